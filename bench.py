@@ -8,7 +8,13 @@ image normalisation (A18) -> 2-D and 3-D backbones -> projection fusion -> FCAF3
 backward -> gradient all-reduce (N > 1) -> clip + AdamW.  The timed region rotates through `--rotate` distinct batches.
 Prints ONE JSON line (rank 0).
 
+A plain run only sets up, warms up, times `--steps` steps and prints the line.  `--full` adds everything else the benchmark
+measures or checks: the instrumented extra steps behind `roofline`, `scatter_path` and `stage_ms`, the CPU oracle's
+`cpu_baseline` with the `parity` check, the replica checks of N > 1 runs and BASELINE configs 4 and 5 plus the from-files leg
+as `other_configs`.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32).
+
   python bench.py --gpus 1 --steps 8 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
 """
@@ -277,6 +283,28 @@ def emit(out, name='bench_detail.json'):
 
 
 
+DUMP_SAMPLE = 1 << 22                 # --dump-outputs: elements of the parameter / gradient samples (16 MB each in float32)
+
+
+def dump_outputs(path, det, losses):
+    """--dump-outputs: what the last timed train step hands its caller -- the losses it returned, the parameters and buffers it
+    left in the arena and the gradients it applied -- as float32 .npy files under `path`.  The arena holds ~86 M floats, so the
+    parameters and gradients are a fixed sample: the same DUMP_SAMPLE sorted indices on every run (seeded), written as values only."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in losses.items():
+        name = ''.join(c if (c.isalnum() or c in '_-.') else '_' for c in k)
+        np.save(os.path.join(path, f'{name}.npy'), torch.as_tensor(v).detach().float().reshape(-1).cpu().numpy())
+    rng = np.random.default_rng(0)
+    a = det.arena
+    for name, t in (('params_sample', a.data), ('grads_sample', a.grad)):
+        n = t.numel()
+        idx = np.sort(rng.choice(n, min(n, DUMP_SAMPLE), replace=False))
+        np.save(os.path.join(path, f'{name}.npy'), t[torch.from_numpy(idx).to(t.device)].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -285,12 +313,12 @@ def main():
     ap.add_argument('--batch', type=int, default=4, help='scans per GPU per step (reference config: 8xb4)')
     ap.add_argument('--views', type=int, default=20)
     ap.add_argument('--rotate', type=int, default=3, help='distinct synthetic batches the timed steps cycle through')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and its parity check')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'f32'],
                     help='conv fwd/dgrad matrix-core type: bf16 MFMA with f32 accumulate (BASELINE config) or exact-f32 MFMA')
     ap.add_argument('--resident', action='store_true', help='skip the per-step host->device copy (inputs resident in HBM)')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip BASELINE configs 4 (mv-grounding) and 5 (occupancy), which the default 1-GPU run appends as `other_configs`')
+                    help='skip BASELINE configs 4 (mv-grounding) and 5 (occupancy), which a 1-GPU --full run appends as `other_configs`')
     ap.add_argument('--only', default=None, choices=['grounding', 'occupancy', 'from_files'],
                     help='run ONLY that configuration and print its object as the JSON line (profiling passes)')
     ap.add_argument('--grounding-batch', type=int, default=12, help='scans per GPU per step of config 4 (reference: 8xb12)')
@@ -298,7 +326,16 @@ def main():
     ap.add_argument('--dry-launch', action='store_true',
                     help='N > 1 plumbing check without a GPU: every rank joins the process group (ES_DIST_BACKEND, default gloo here), '
                          'all-reduces a token, rank 0 prints one JSON line')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the instrumented extra steps (roofline, scatter path, stage times), the CPU '
+                         'baseline with its parity check, the replica checks of N > 1 and the other configurations (see --no-cpu-baseline, '
+                         '--no-other-configs); a plain run only times the steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (its losses, a fixed seeded sample of the parameters it left and of '
+                         'the gradients it applied) to DIR/<name>.npy in float32')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): become the launcher -- one rank per GPU
     # under torch.distributed.run on 127.0.0.1 (the container hostname may not resolve), same arguments, same stdout.  The
@@ -361,7 +398,7 @@ def main():
     # weights on the HIP path; cpu_baseline() below runs the oracle on the same scan / weights and asserts agreement
     parity_hip = None
     sd0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sd0 = {k: v.cpu() for k, v in det.state_dict().items()}
         d0 = pipeline.upload_scan(scans[0], dev)
         b0 = pipeline.make_batch([d0])
@@ -412,7 +449,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # time EXACTLY `steps` steps; the convolution engine launches of ONE EXTRA step after them are bracketed by HIP events
+    # time EXACTLY `steps` steps; with --full the convolution engine launches of ONE EXTRA step after them are bracketed by HIP events
     # recorded on the stream each kernel is launched on (the step runs on four compute streams + the copy stream)
     prof = {'names': ENGINE, 'records': [], 'event': lambda: torch.cuda.Event(enable_timing=True)}
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -428,21 +465,25 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     host = host_report(cfs0)
-    # one extra UNTIMED step on the same (four-stream) schedule with every engine launch bracketed by HIP events (2 events per
-    # launch and a pair counter per kernel map cost ~3 ms of host time, and instrumented launches cannot be replayed from the
-    # image backbone's hipGraph -- so this step is kept out of the timed region since round 3)
-    hip.PROFILE = prof
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, det, losses)            # before anything else moves the weights
     red = getattr(det.arena, 'reducer', None)
-    if red is not None:
-        red.profile = []                                        # N > 1: how long the optimiser waits for each gradient bucket
-    step(prefetch_next=False)                                   # (consumes the batch the last timed step prepared)
-    recs = resolve_pairs(hip, prof['records'])
-    torch.cuda.synchronize()
-    hip.PROFILE = None
-    if red is not None:
-        prof_red, red.profile = red.profile, None
+    recs = prof_red = None
+    if args.full:
+        # one extra UNTIMED step on the same (four-stream) schedule with every engine launch bracketed by HIP events (2 events per
+        # launch and a pair counter per kernel map cost ~3 ms of host time, and instrumented launches cannot be replayed from the
+        # image backbone's hipGraph -- so this step is kept out of the timed region since round 3)
+        hip.PROFILE = prof
+        if red is not None:
+            red.profile = []                                    # N > 1: how long the optimiser waits for each gradient bucket
+        step(prefetch_next=False)                               # (consumes the batch the last timed step prepared)
+        recs = resolve_pairs(hip, prof['records'])
+        torch.cuda.synchronize()
+        hip.PROFILE = None
+        if red is not None:
+            prof_red, red.profile = red.profile, None
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
-    in_sync = True
+    in_sync = None
     rank_ms = None
     if world > 1:
         # per-rank time of the timed region (voxel counts differ per rank -> stragglers; SURVEY 8e asks for the spread)
@@ -451,6 +492,7 @@ def main():
         per = sorted(float(t.item()) / args.steps * 1e3 for t in every)
         rank_ms = dict(min=round(per[0], 3), median=round(per[len(per) // 2], 3), max=round(per[-1], 3))
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    if world > 1 and args.full:
         # data-parallel sanity (outside the timed region): every replica must hold the same parameters
         chk = det.arena.data[:det.arena.n_train].double().abs().sum().reshape(1)
         lo, hi = chk.clone(), chk.clone()
@@ -469,101 +511,104 @@ def main():
             dist.destroy_process_group()
         return
 
-    mfma_peak = K_PEAK_MFMA[args.precision]
-    eng = engine_totals(recs, mfma_peak)
+    # ---- --full: the roofline of the convolution engine, the scatter path and per-stage times from untimed extra steps
+    roofline = scatter = stages = None
+    if args.full:
+        mfma_peak = K_PEAK_MFMA[args.precision]
+        eng = engine_totals(recs, mfma_peak)
 
-    # ---- one extra UNTIMED step on the single-stream schedule: stand-alone duration of every engine launch, the
-    # scatter-path kernels (north_star: "achieved HBM GB/s for the scatter path") and per-stage times
-    single = scatter = stages = classes = None
-    if world == 1:
-        saved = (E.TWO_STREAMS[0], E.WGRAD_ASYNC[0])
-        E.TWO_STREAMS[0] = E.WGRAD_ASYNC[0] = False
-        stages = stage_times(lambda: step(prefetch_next=False))     # median of 3 warmed serial steps (coordinate phase inside)
-        prof1 = dict(prof, names=ENGINE | SCATTER, records=[])
-        hip.PROFILE = prof1
-        step(prefetch_next=False)                                   # + one with every engine / scatter launch bracketed
-        hip.PROFILE = None
-        E.TWO_STREAMS[0], E.WGRAD_ASYNC[0] = saved
-        r1 = resolve_pairs(hip, prof1['records'])
-        torch.cuda.synchronize()
-        e1 = engine_totals([r for r in r1 if r[0] in ENGINE], mfma_peak)
-        single = dict(kernel_ms_per_step=e1['ms'], launches=e1['launches'], algorithmic_tflops=e1['tflops'],
-                      frac_of_binding_roof=e1['frac_binding'], pair_bytes_GBps=e1['pair_GBps'],
-                      note='same launches, one extra untimed step with ES_TWO_STREAMS=0 ES_WGRAD_ASYNC=0 (stand-alone '
-                           'durations); rocprofv3 summary of this schedule: profiles/r3_single_stream_kernel_stats.txt')
-        scatter = scatter_totals([r for r in r1 if r[0] in SCATTER])
-        classes = launch_classes(r1, mfma_peak)
-        if os.environ.get('ES_BENCH_DUMP'):                     # dev: every engine launch of the single-stream step, in order
-            with open(os.environ['ES_BENCH_DUMP'], 'w') as f:
-                for name, ev0, ev1, a, _ in r1:
-                    if name in ENGINE:
-                        nbr, n_out, n_in, K, cin, cout = engine_args(name, a)
-                        f.write(json.dumps(dict(fn=name, K=K, cin=cin, cout=cout, n_out=n_out, n_in=n_in, map=bool(nbr),
-                                                us=round(ev0.elapsed_time(ev1) * 1e3, 1),
-                                                args=[x for x in a if isinstance(x, int) and abs(x) < (1 << 31)])) + '\n')
-        stages['_note'] = 'single-stream schedule (ES_TWO_STREAMS=0 ES_WGRAD_ASYNC=0): HIP-event time between stage boundaries, MEDIAN of 3 ' \
-                          'untimed steps after one warm-up step on that schedule; includes host-induced gaps; the default four-stream ' \
-                          'schedule overlaps A7 with A4-A6 and the two backward branches'
+        # ---- one extra UNTIMED step on the single-stream schedule: stand-alone duration of every engine launch, the
+        # scatter-path kernels (north_star: "achieved HBM GB/s for the scatter path") and per-stage times
+        single = scatter = stages = classes = None
+        if world == 1:
+            saved = (E.TWO_STREAMS[0], E.WGRAD_ASYNC[0])
+            E.TWO_STREAMS[0] = E.WGRAD_ASYNC[0] = False
+            stages = stage_times(lambda: step(prefetch_next=False))     # median of 3 warmed serial steps (coordinate phase inside)
+            prof1 = dict(prof, names=ENGINE | SCATTER, records=[])
+            hip.PROFILE = prof1
+            step(prefetch_next=False)                                   # + one with every engine / scatter launch bracketed
+            hip.PROFILE = None
+            E.TWO_STREAMS[0], E.WGRAD_ASYNC[0] = saved
+            r1 = resolve_pairs(hip, prof1['records'])
+            torch.cuda.synchronize()
+            e1 = engine_totals([r for r in r1 if r[0] in ENGINE], mfma_peak)
+            single = dict(kernel_ms_per_step=e1['ms'], launches=e1['launches'], algorithmic_tflops=e1['tflops'],
+                          frac_of_binding_roof=e1['frac_binding'], pair_bytes_GBps=e1['pair_GBps'],
+                          note='same launches, one extra untimed step with ES_TWO_STREAMS=0 ES_WGRAD_ASYNC=0 (stand-alone '
+                               'durations); rocprofv3 summary of this schedule: profiles/r3_single_stream_kernel_stats.txt')
+            scatter = scatter_totals([r for r in r1 if r[0] in SCATTER])
+            classes = launch_classes(r1, mfma_peak)
+            if os.environ.get('ES_BENCH_DUMP'):                     # dev: every engine launch of the single-stream step, in order
+                with open(os.environ['ES_BENCH_DUMP'], 'w') as f:
+                    for name, ev0, ev1, a, _ in r1:
+                        if name in ENGINE:
+                            nbr, n_out, n_in, K, cin, cout = engine_args(name, a)
+                            f.write(json.dumps(dict(fn=name, K=K, cin=cin, cout=cout, n_out=n_out, n_in=n_in, map=bool(nbr),
+                                                    us=round(ev0.elapsed_time(ev1) * 1e3, 1),
+                                                    args=[x for x in a if isinstance(x, int) and abs(x) < (1 << 31)])) + '\n')
+            stages['_note'] = 'single-stream schedule (ES_TWO_STREAMS=0 ES_WGRAD_ASYNC=0): HIP-event time between stage boundaries, MEDIAN of 3 ' \
+                              'untimed steps after one warm-up step on that schedule; includes host-induced gaps; the default four-stream ' \
+                              'schedule overlaps A7 with A4-A6 and the two backward branches'
 
-    # static PMC figures of the same command (separate rocprofv3 --pmc passes, see profiles/): bytes per engine launch
-    traffic, traffic_extra, traffic_note = None, {}, 'traffic: null (no PMC summary for this precision under profiles/)'
-    for name in ('r6_pmc_traffic.json', 'r5_pmc_traffic.json', 'r4_pmc_traffic.json', 'r3_pmc_traffic.json', 'r2_pmc_traffic.json', 'r1_final_pmc_traffic.json'):
-        pmc_file = os.path.join(ROOT, 'profiles', name)
-        if args.precision == 'bf16' and os.path.exists(pmc_file):
-            pmc = json.load(open(pmc_file))
-            traffic = pmc['bytes_per_launch']
-            # `traffic` is per launch of the PMC family (the engine kernels AND their reduction helpers); multiply by ITS launch
-            # count -- not by roofline.launches_per_step, which counts engine entry points -- to get the bytes per step
-            traffic_extra = dict(traffic_launches_per_step=pmc['launches'] // pmc['steps'], traffic_bytes_per_step=pmc['bytes_per_step'],
-                                 traffic_source=f'profiles/{name}')
-            traffic_note = (f"traffic is STATIC: HBM bytes per launch of the convolution-engine kernel family from the committed PMC passes "
-                            f"of this command (profiles/{name}: {pmc['bytes_per_step'] / 1e9:.1f} GB per step over "
-                            f"{pmc['launches'] // pmc['steps']} kernel launches = traffic x traffic_launches_per_step), not re-measured by this run")
-            break
-    # achieved / frac / kernel_ms_per_step come from the STAND-ALONE durations (the extra single-stream step, = what a rocprofv3 kernel
-    # trace of that schedule sums: profiles/r5_single_stream_kernel_stats.txt) when this is a one-GPU run: HIP-event brackets under the
-    # four-stream schedule overlap in time and over-count (round-4 finding: 29.3 ms of "kernel time" in a 25.6 ms step); the concurrent
-    # figures stay in `concurrent_schedule`
-    # Round 6: ONE definition, kept from here on -- the family's launches on the DEFAULT (four-stream) schedule, HIP-event
-    # duration of each launch on its own stream, summed (an upper bound of what a rocprofv3 kernel trace of the same schedule sums:
-    # events also see the time a launch waits for a free CU); the stand-alone figure of the single-stream extra step stays beside it
-    # as `frac_standalone`, the dominant launch class (stand-alone durations) as `dominant`.
-    base = eng
-    if base['t_mfma'] >= base['t_hbm']:
-        roof = dict(bound='mfma', achieved=base['tflops'], peak=mfma_peak, unit='TFLOP/s',
-                    frac=round(base['tflops'] / mfma_peak, 4))
-    else:
-        roof = dict(bound='hbm', achieved=base['comp_GBps'], peak=K_PEAK_HBM, unit='GB/s',
-                    frac=round(base['comp_GBps'] / K_PEAK_HBM, 4))
-    roofline = dict(roof, traffic=traffic, **traffic_extra,
-                    kernel='convolution engine: k_spconv_* (gather / halo / narrow) / k_rowgemm2 / k_lin_small / k_expand / k_img_conv3 (fwd, dgrad) + k_spconv_wgrad_bf16* / k_img_wgrad9 / k_rows_wgrad1' if args.precision == 'bf16'
-                    else 'convolution engine: k_spconv / k_spconv_wgrad (exact-f32 MFMA)',
-                    launches_per_step=base['launches'], kernel_ms_per_step=base['ms'],
-                    frac_of_binding_roof=base['frac_binding'],
-                    durations='HIP events per launch, default four-stream schedule, one extra step after the timed ones',
-                    frac_standalone=(None if single is None else round(
-                        (e1['tflops'] / mfma_peak) if roof['bound'] == 'mfma' else (e1['comp_GBps'] / K_PEAK_HBM), 4)),
-                    dominant=(None if not classes else dict(cls=classes[0]['cls'], launches=classes[0]['launches'], ms=classes[0]['ms'],
-                                                           tflops=classes[0]['tflops'], frac_mfma=round(classes[0]['tflops'] / mfma_peak, 4),
-                                                           frac_of_binding_roof=classes[0]['frac_of_binding_roof'])),
-                    concurrent_schedule=dict(kernel_ms_per_step=eng['ms'], achieved_GBps=eng['comp_GBps'], tflops=eng['tflops'],
-                                             frac_of_binding_roof=eng['frac_binding']),
-                    mfma=dict(achieved_tflops=base['tflops'], peak_tflops=mfma_peak, frac=round(base['tflops'] / mfma_peak, 4)),
-                    hbm_compulsory=dict(achieved_GBps=base['comp_GBps'], frac=round(base['comp_GBps'] / K_PEAK_HBM, 4),
-                                        bytes_per_step=base['comp_bytes']),
-                    hbm_pair_bytes=dict(achieved_GBps=base['pair_GBps'], frac=round(base['pair_GBps'] / K_PEAK_HBM, 4),
-                                        bytes_per_step=base['pair_bytes']),
-                    single_stream=single, classes=classes,
-                    note='per launch: algorithmic flops = 2*P*Cin*Cout (P = valid (output,tap) pairs), compulsory bytes = '
-                         'every input row, output row and weight once, pair bytes = SURVEY 8(d) P*(Cin+Cout)*4 + weights; '
-                         'binding roof per launch = max(flops/MFMA peak, compulsory bytes/HBM peak); frac_of_binding_roof = '
-                         'sum of binding-roof times / sum of HIP-event launch durations; bound/achieved/peak/frac = the '
-                         'roof that binds the family in total; durations (see `durations`) are HIP-event times on the launch stream: stand-alone = '
-                         'one extra single-stream step (round 5: the headline figures); under the '
-                         'concurrent 4-stream schedule (kernels of different streams share the chip, so the sum exceeds wall '
-                         'time), taken on ONE EXTRA untimed step right after the timed ones -- per-launch events cost ~3 ms of '
-                         'host time and keep the image backbone off its hipGraph, so the timed steps carry no instrumentation; classes = the top engine launch classes of the single-stream step (stand-alone durations); '
-                         + traffic_note)
+        # static PMC figures of the same command (separate rocprofv3 --pmc passes, see profiles/): bytes per engine launch
+        traffic, traffic_extra, traffic_note = None, {}, 'traffic: null (no PMC summary for this precision under profiles/)'
+        for name in ('r6_pmc_traffic.json', 'r5_pmc_traffic.json', 'r4_pmc_traffic.json', 'r3_pmc_traffic.json', 'r2_pmc_traffic.json', 'r1_final_pmc_traffic.json'):
+            pmc_file = os.path.join(ROOT, 'profiles', name)
+            if args.precision == 'bf16' and os.path.exists(pmc_file):
+                pmc = json.load(open(pmc_file))
+                traffic = pmc['bytes_per_launch']
+                # `traffic` is per launch of the PMC family (the engine kernels AND their reduction helpers); multiply by ITS launch
+                # count -- not by roofline.launches_per_step, which counts engine entry points -- to get the bytes per step
+                traffic_extra = dict(traffic_launches_per_step=pmc['launches'] // pmc['steps'], traffic_bytes_per_step=pmc['bytes_per_step'],
+                                     traffic_source=f'profiles/{name}')
+                traffic_note = (f"traffic is STATIC: HBM bytes per launch of the convolution-engine kernel family from the committed PMC passes "
+                                f"of this command (profiles/{name}: {pmc['bytes_per_step'] / 1e9:.1f} GB per step over "
+                                f"{pmc['launches'] // pmc['steps']} kernel launches = traffic x traffic_launches_per_step), not re-measured by this run")
+                break
+        # achieved / frac / kernel_ms_per_step come from the STAND-ALONE durations (the extra single-stream step, = what a rocprofv3 kernel
+        # trace of that schedule sums: profiles/r5_single_stream_kernel_stats.txt) when this is a one-GPU run: HIP-event brackets under the
+        # four-stream schedule overlap in time and over-count (round-4 finding: 29.3 ms of "kernel time" in a 25.6 ms step); the concurrent
+        # figures stay in `concurrent_schedule`
+        # Round 6: ONE definition, kept from here on -- the family's launches on the DEFAULT (four-stream) schedule, HIP-event
+        # duration of each launch on its own stream, summed (an upper bound of what a rocprofv3 kernel trace of the same schedule sums:
+        # events also see the time a launch waits for a free CU); the stand-alone figure of the single-stream extra step stays beside it
+        # as `frac_standalone`, the dominant launch class (stand-alone durations) as `dominant`.
+        base = eng
+        if base['t_mfma'] >= base['t_hbm']:
+            roof = dict(bound='mfma', achieved=base['tflops'], peak=mfma_peak, unit='TFLOP/s',
+                        frac=round(base['tflops'] / mfma_peak, 4))
+        else:
+            roof = dict(bound='hbm', achieved=base['comp_GBps'], peak=K_PEAK_HBM, unit='GB/s',
+                        frac=round(base['comp_GBps'] / K_PEAK_HBM, 4))
+        roofline = dict(roof, traffic=traffic, **traffic_extra,
+                        kernel='convolution engine: k_spconv_* (gather / halo / narrow) / k_rowgemm2 / k_lin_small / k_expand / k_img_conv3 (fwd, dgrad) + k_spconv_wgrad_bf16* / k_img_wgrad9 / k_rows_wgrad1' if args.precision == 'bf16'
+                        else 'convolution engine: k_spconv / k_spconv_wgrad (exact-f32 MFMA)',
+                        launches_per_step=base['launches'], kernel_ms_per_step=base['ms'],
+                        frac_of_binding_roof=base['frac_binding'],
+                        durations='HIP events per launch, default four-stream schedule, one extra step after the timed ones',
+                        frac_standalone=(None if single is None else round(
+                            (e1['tflops'] / mfma_peak) if roof['bound'] == 'mfma' else (e1['comp_GBps'] / K_PEAK_HBM), 4)),
+                        dominant=(None if not classes else dict(cls=classes[0]['cls'], launches=classes[0]['launches'], ms=classes[0]['ms'],
+                                                               tflops=classes[0]['tflops'], frac_mfma=round(classes[0]['tflops'] / mfma_peak, 4),
+                                                               frac_of_binding_roof=classes[0]['frac_of_binding_roof'])),
+                        concurrent_schedule=dict(kernel_ms_per_step=eng['ms'], achieved_GBps=eng['comp_GBps'], tflops=eng['tflops'],
+                                                 frac_of_binding_roof=eng['frac_binding']),
+                        mfma=dict(achieved_tflops=base['tflops'], peak_tflops=mfma_peak, frac=round(base['tflops'] / mfma_peak, 4)),
+                        hbm_compulsory=dict(achieved_GBps=base['comp_GBps'], frac=round(base['comp_GBps'] / K_PEAK_HBM, 4),
+                                            bytes_per_step=base['comp_bytes']),
+                        hbm_pair_bytes=dict(achieved_GBps=base['pair_GBps'], frac=round(base['pair_GBps'] / K_PEAK_HBM, 4),
+                                            bytes_per_step=base['pair_bytes']),
+                        single_stream=single, classes=classes,
+                        note='per launch: algorithmic flops = 2*P*Cin*Cout (P = valid (output,tap) pairs), compulsory bytes = '
+                             'every input row, output row and weight once, pair bytes = SURVEY 8(d) P*(Cin+Cout)*4 + weights; '
+                             'binding roof per launch = max(flops/MFMA peak, compulsory bytes/HBM peak); frac_of_binding_roof = '
+                             'sum of binding-roof times / sum of HIP-event launch durations; bound/achieved/peak/frac = the '
+                             'roof that binds the family in total; durations (see `durations`) are HIP-event times on the launch stream: stand-alone = '
+                             'one extra single-stream step (round 5: the headline figures); under the '
+                             'concurrent 4-stream schedule (kernels of different streams share the chip, so the sum exceeds wall '
+                             'time), taken on ONE EXTRA untimed step right after the timed ones -- per-launch events cost ~3 ms of '
+                             'host time and keep the image backbone off its hipGraph, so the timed steps carry no instrumentation; classes = the top engine launch classes of the single-stream step (stand-alone durations); '
+                             + traffic_note)
 
     out = dict(metric='scans/sec (train step) mv-3ddet, 20x(480x640) RGB-D views', value=round(world * args.batch * args.steps / dt, 4),
                unit='scans/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -584,7 +629,8 @@ def main():
     out['dist_backend'] = None                                   # one process, no process group
     if world > 1:
         out['dist_backend'] = dist.get_backend() + (' (RCCL)' if dist.get_backend() == 'nccl' else '')
-        out['replicas_in_sync'] = in_sync
+        if args.full:
+            out['replicas_in_sync'] = in_sync
         out['rank_ms_per_step'] = rank_ms
         if red is not None and prof_red:
             exposed, mb = {}, {}
@@ -601,11 +647,11 @@ def main():
     out['host'] = host
     # GPU-side duration of each timed step (events on the main stream)
     out['step_ms'] = [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(args.steps)]
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'], out['parity'] = cpu_baseline(scans[0], sd0, det, parity_hip, args)
     # ---- BASELINE configs 4 and 5 on the same GPU, same rules (H2D in the step, rotating batches, parity vs the oracle)
     bad = []
-    if world == 1 and not args.no_other_configs:
+    if args.full and world == 1 and not args.no_other_configs:
         del det, optim, feeder, scans, losses
         E.TAPE.clear()
         release_frozen()

@@ -70,3 +70,37 @@ def test_emit_prints_the_short_line_last(tmp_path, capsys, monkeypatch):
     for p in (tmp_path / 'bench_detail.json', tmp_path / 'gpurun_out' / 'bench_detail.json'):
         assert json.load(open(p))['value'] == full['value']            # the long form is on disk, complete
     assert line['detail'] == 'bench_detail.json'
+
+
+def test_plain_and_full_runs_are_separate_options():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the steps only; the other figures sit behind --full"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    for opt in ('--full', '--dump-outputs', '--steps', '--warmup', '--gpus'):
+        assert opt in r.stdout, opt
+
+
+def test_dump_outputs_is_a_fixed_float32_sample_under_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs: losses + the same seeded sample of the parameter arena and the gradients on every run, float32, <= 64 MB"""
+    import types
+    import numpy as np
+    import torch
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
+    g = torch.Generator().manual_seed(0)
+    arena = types.SimpleNamespace(data=torch.randn(3 * bench.DUMP_SAMPLE, generator=g), grad=torch.randn(2 * bench.DUMP_SAMPLE, generator=g))
+    det = types.SimpleNamespace(arena=arena)
+    losses = {'loss_center': torch.tensor(0.5, requires_grad=True), 'loss_bbox': torch.tensor(1.25), 'loss_cls': torch.tensor(2.0)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), det, losses)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['grads_sample.npy', 'loss_bbox.npy', 'loss_center.npy', 'loss_cls.npy', 'params_sample.npy']
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 * 2 ** 20
+    assert float(np.load(tmp_path / 'a' / 'loss_bbox.npy')[0]) == 1.25
+    p = np.load(tmp_path / 'a' / 'params_sample.npy')
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.isin(p, arena.data.numpy()).all()

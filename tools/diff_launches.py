@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""dev tool: per-launch-class A/B of two `ES_BENCH_DUMP=<file> python bench.py ...` dumps (every engine launch of one
+"""dev tool: per-launch-class A/B of two `ES_BENCH_DUMP=<file> python bench.py --full ...` dumps (every engine launch of one
 single-stream step with its entry point, shape and stand-alone duration).  Launches are grouped by (entry point, K, C_in,
 C_out, n_out); prints launches, total us in A and B, the difference, worst first.
 
-  ES_BENCH_DUMP=a.jsonl python bench.py --no-cpu-baseline --no-other-configs --steps 4 --warmup 2
-  ES_BENCH_DUMP=b.jsonl ES_DMA_MIN_CIN=0 python bench.py --no-cpu-baseline --no-other-configs --steps 4 --warmup 2
+  ES_BENCH_DUMP=a.jsonl python bench.py --full --no-cpu-baseline --no-other-configs --steps 4 --warmup 2
+  ES_BENCH_DUMP=b.jsonl ES_DMA_MIN_CIN=0 python bench.py --full --no-cpu-baseline --no-other-configs --steps 4 --warmup 2
   python tools/diff_launches.py a.jsonl b.jsonl [--by kind]      # kind: fwd/dgrad vs wgrad x K x channels only"""
 import argparse
 import json

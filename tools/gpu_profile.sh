@@ -14,7 +14,7 @@ run_prof () {   # name, extra rocprof args..., then -- command
   echo "rocprof $name rc $?"
 }
 db () { find /tmp/prof_$1 -name '*.db' | head -1; }
-CMD="python $B --no-cpu-baseline --no-other-configs --steps 4 --warmup 2"
+CMD="python $B --full --no-cpu-baseline --no-other-configs --steps 4 --warmup 2"
 # 1. kernel trace, default four-stream schedule and single-stream schedule
 run_prof ks --stats -d /tmp/prof_ks -o p -- $CMD
 python tools/rocpd_stats.py "$(db ks)" $OUT/r3_kernel_stats.txt > /dev/null

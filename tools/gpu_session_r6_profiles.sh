@@ -9,10 +9,10 @@ OUT="$GRAFT_REPO_ROOT/gpurun_out"
 mkdir -p "$OUT"
 B="$GRAFT_REPO_ROOT/bench.py"
 db () { find /tmp/prof_$1 -name '*.db' | head -1; }
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/${T}_bench_default_line.json 2> $OUT/${T}_bench_default.err; echo "bench rc $?"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/${T}_bench_default_line.json 2> $OUT/${T}_bench_default.err; echo "bench rc $?"
 cp bench_detail.json $OUT/${T}_bench_default_detail.json
 tail -c 2200 $OUT/${T}_bench_default_line.json
-CMD="python $B --no-cpu-baseline --no-other-configs --steps 4 --warmup 2"
+CMD="python $B --full --no-cpu-baseline --no-other-configs --steps 4 --warmup 2"
 (cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof_ks -o p -- $CMD > /tmp/prof_ks.log 2>&1); echo "rc $?"
 python tools/rocpd_stats.py "$(db ks)" $OUT/${T}_kernel_stats.txt > /dev/null
 python tools/rocpd_critical.py "$(db ks)" > $OUT/${T}_critical_chain.txt 2>&1

@@ -41,7 +41,7 @@ def main():
     ap.add_argument('--steps', type=int, default=0, help='train steps the profiled command executed (timed + warm-up + extra); 0: the number of optimiser launches (k_adamw*) in the table')
     ap.add_argument('--fetch', required=True)
     ap.add_argument('--write', required=True)
-    ap.add_argument('--command', default='python bench.py --no-cpu-baseline --no-other-configs --steps 4 --warmup 2')
+    ap.add_argument('--command', default='python bench.py --full --no-cpu-baseline --no-other-configs --steps 4 --warmup 2')
     a = ap.parse_args()
     f, w = table(a.fetch), table(a.write)
     if a.steps <= 0:
