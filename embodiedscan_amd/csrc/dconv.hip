@@ -534,13 +534,34 @@ static void dc_roles(int mode, int Cin, int Cout, int& Kd, int& N) {
   Kd = back ? Cout : Cin; N = back ? Cin : Cout;
 }
 
-extern "C" int es_dconv_supported(const int* geom_host, int mode, int Cin, int Cout) {
-  DcGeom g; int M, ns;
-  if (dc_geometry(geom_host, mode, g, M, ns) != 0) return 0;
-  if (mode == 2 || mode == 5) return (Cin % 256 == 0 && Cout % 256 == 0) ? 1 : 0;
+// the whole gate of both launchers: geometry, channels, the operands' layout and alignment and the 32-bit index range.  Modes 0 / 1 / 3 / 4:
+// A = the source rows, B = the result rows; modes 2 / 5: A = X, B = dY (the weight-gradient operands).  A null pointer: a fresh buffer
+// (es_dconv_supported asks for fresh contiguous operands).
+static int dconv_check(const int* geom_host, int mode, int Cin, int Cout, const void* A, int lda, const void* B, int ldb, const void* W_bf16,
+                       DcGeom& g, int& M, int& ns) {
+  const int rc = dc_geometry(geom_host, mode, g, M, ns);
+  if (rc != 0) return rc;
+  if (mode == 2 || mode == 5) {
+    const long long nx = mode == 5 ? M : ns, ny = mode == 5 ? ns : M;     // rows of X / of dY
+    if (Cin % 256 != 0 || Cout % 256 != 0 || (lda & 7) != 0 || (ldb & 7) != 0 || ((uintptr_t)A & 15) != 0 || ((uintptr_t)B & 15) != 0 ||
+        nx * lda >= (1ll << 31) || ny * ldb >= (1ll << 31))
+      return -4;
+    return 0;
+  }
   int Kd, N;
   dc_roles(mode, Cin, Cout, Kd, N);
-  return (Kd % 64 == 0 && N % 128 == 0) ? 1 : 0;
+  const int nTw = mode >= 3 ? 8 : g.nT;           // taps of the weight tensor
+  if (Kd % 64 != 0 || N % 128 != 0 || (lda & 7) != 0 || (ldb & 3) != 0 || ((uintptr_t)A & 15) != 0 || ((uintptr_t)W_bf16 & 15) != 0 ||
+      ((uintptr_t)B & 15) != 0 || (long long)ns * lda >= (1ll << 31) || (long long)(nTw > 27 ? nTw : 27) * N * Kd >= (1ll << 31))
+    return -4;
+  return 0;
+}
+
+// (for fresh contiguous operands; the launchers answer for the caller's own with -4)
+extern "C" int es_dconv_supported(const int* geom_host, int mode, int Cin, int Cout) {
+  DcGeom g; int M, ns;
+  const bool back = mode == 1 || mode == 4;          // data gradients: source rows of Cout channels, result rows of Cin
+  return dconv_check(geom_host, mode, Cin, Cout, nullptr, back ? Cout : Cin, nullptr, back ? Cin : Cout, nullptr, g, M, ns) == 0 ? 1 : 0;
 }
 
 extern "C" size_t es_dconv_workspace_floats(const int* geom_host, int mode, int Cin, int Cout) {
@@ -559,14 +580,10 @@ extern "C" int es_dconv_fwd_bf16(const void* Xh, int ldx, const void* W_bf16, co
                                  float* Y, int ldy, int accumulate, float* ws, size_t ws_floats, void* stream) {
   DcGeom g; int M, ns;
   if (mode != 0 && mode != 1 && mode != 3 && mode != 4) return -2;
-  int rc = dc_geometry(geom_host, mode, g, M, ns);
+  int rc = dconv_check(geom_host, mode, Cin, Cout, Xh, ldx, Y, ldy, W_bf16, g, M, ns);
   if (rc != 0) return rc;
   int Kd, N;
   dc_roles(mode, Cin, Cout, Kd, N);
-  const int nTw = mode >= 3 ? 8 : g.nT;           // taps of the weight tensor
-  if (Kd % 64 != 0 || N % 128 != 0 || (ldx & 7) != 0 || (ldy & 3) != 0 || ((uintptr_t)Xh & 15) != 0 || ((uintptr_t)W_bf16 & 15) != 0 ||
-      ((uintptr_t)Y & 15) != 0 || (long long)ns * ldx >= (1ll << 31) || (long long)(nTw > 27 ? nTw : 27) * N * Kd >= (1ll << 31))
-    return -4;
   DcPlan p = dc_plan(M, N, (Kd / 64) * g.nT, g.cls, g.nT);
   if (p.nsplit > 1 && (ws == nullptr || ws_floats < (size_t)p.nsplit * (g.cls ? 8 : 1) * M * N || ((uintptr_t)ws & 15) != 0)) return -5;
   hipStream_t st = (hipStream_t)stream;
@@ -621,12 +638,8 @@ extern "C" size_t es_dconv_wgrad_workspace_floats(const int* geom_host, int tran
 static int dconv_wgrad_impl(const void* Xh, int ldx, const void* dYh, int ldy, const int* geom_host, int transposed, int Cin, int Cout,
                             float* dW, int accumulate, float* ws, size_t ws_floats, int allow_split, void* stream) {
   DcGeom g; int M, ns;
-  int rc = dc_geometry(geom_host, transposed ? 5 : 2, g, M, ns);
+  int rc = dconv_check(geom_host, transposed ? 5 : 2, Cin, Cout, Xh, ldx, dYh, ldy, nullptr, g, M, ns);
   if (rc != 0) return rc;
-  const long long nx = transposed ? M : ns, ny = transposed ? ns : M;     // rows of X / of dY
-  if (Cin % 256 != 0 || Cout % 256 != 0 || (ldx & 7) != 0 || (ldy & 7) != 0 || ((uintptr_t)Xh & 15) != 0 || ((uintptr_t)dYh & 15) != 0 ||
-      nx * ldx >= (1ll << 31) || ny * ldy >= (1ll << 31))
-    return -4;
   const int nCo = Cout / 256, nwg = g.nT * (Cin / 256) * nCo;
   const int ms = allow_split ? dc_wgrad_split(nwg, M) : 1;
   const size_t tot = (size_t)g.nT * Cin * Cout;

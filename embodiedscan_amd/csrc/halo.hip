@@ -376,10 +376,15 @@ extern "C" int es_halo_set_option(int key, int value) {
   return -1;
 }
 
+// the shape, layout, alignment and 32-bit index range the kernel takes (a null pointer: a fresh buffer)
+static bool halo_check(int n_in, int ldx, int K, int Cin, int Cout, const void* Xh, const void* W_bf16, const void* loc) {
+  if (K != HL_K || (Cin % 64) || (Cout % 128) || (ldx % 8) || ((((uintptr_t)Xh) | ((uintptr_t)W_bf16) | ((uintptr_t)loc)) & 15)) return false;
+  return (long long)n_in * ldx < (1ll << 31) && (long long)K * Cout * Cin < (1ll << 31);
+}
+
+// (for fresh source rows; the launcher answers for the caller's own with -4)
 extern "C" int es_spconv_halo_supported(int n_out, int n_in, int ldx, int K, int Cin, int Cout) {
-  if (K != HL_K || n_out <= 0) return 0;
-  if ((Cin % 64) || (Cout % 128) || (ldx % 8)) return 0;
-  if ((long long)n_in * ldx >= (1ll << 31) || (long long)K * Cout * Cin >= (1ll << 31)) return 0;
+  if (n_out <= 0 || !halo_check(n_in, ldx, K, Cin, Cout, nullptr, nullptr, nullptr)) return 0;
   return es_cdiv(n_out, HL_BM) * (Cout / 128) >= ES_OPT_HALO_MIN_WGS ? 1 : 0;
 }
 
@@ -387,8 +392,7 @@ extern "C" int es_spconv_halo_bf16(const void* Xh, int ldx, const void* W_bf16, 
                                    int n_out, int n_in, int K, int Cin, int Cout, const float* bias, float* Y, int ldy,
                                    int accumulate, int mirror, void* stream) {
   if (n_out <= 0) return 0;
-  if (K != HL_K || (Cin % 64) || (Cout % 128) || (ldx % 8) || ((((uintptr_t)Xh) | ((uintptr_t)W_bf16) | ((uintptr_t)loc)) & 15)) return -4;
-  if ((long long)n_in * ldx >= (1ll << 31) || (long long)K * Cout * Cin >= (1ll << 31)) return -4;
+  if (!halo_check(n_in, ldx, K, Cin, Cout, Xh, W_bf16, loc)) return -4;
   const int rowTiles = es_cdiv(n_out, HL_BM), colTiles = Cout / 128, total = rowTiles * colTiles, per = es_cdiv(total, 8);
   const int wgs = ES_OPT_HALO_WGS > 0 ? ES_OPT_HALO_WGS : 256;            // persistent: one workgroup per CU (MI355X: 256 CUs)
   hipLaunchKernelGGL((k_spconv_halo<128>), dim3(8 * per < wgs ? 8 * per : (wgs & ~7)), dim3(512), 0, (hipStream_t)stream, (const unsigned short*)Xh, ldx,

@@ -212,19 +212,27 @@ static bool img_conv_plan(int n_img, int H, int W, int C, int stride, int mode, 
   return true;
 }
 
+// the whole gate of the path: the plan plus the operands' layout, alignment and 32-bit index range (a null pointer: a fresh buffer)
+static bool img_conv_check(int n_img, int H, int W, int C, int stride, int mode, const void* X, int ldx, const void* W_bf16,
+                           const void* Y, int y_half, int ldy, int& wp, int& rows, int& bands) {
+  if (!img_conv_plan(n_img, H, W, C, stride, mode, wp, rows, bands)) return false;
+  if ((ldx % (mode ? 4 : 8)) || ((((uintptr_t)X) | ((uintptr_t)W_bf16)) & 15) || (y_half ? ((ldy % 2) || (((uintptr_t)Y) & 3)) : 0)) return false;
+  if (mode == 1 && y_half) return false;
+  return (long long)n_img * H * W * (ldx > ldy ? ldx : ldy) < (1ll << 31);
+}
+
+// (for fresh contiguous operands; the launcher answers for the caller's own with -4)
 extern "C" int es_img_conv3_supported(int n_img, int H, int W, int C, int stride, int mode) {
   int wp, rows, bands;
-  return img_conv_plan(n_img, H, W, C, stride, mode, wp, rows, bands) ? 1 : 0;
+  return img_conv_check(n_img, H, W, C, stride, mode, nullptr, C, nullptr, nullptr, 0, C, wp, rows, bands) ? 1 : 0;
 }
 
 extern "C" int es_img_conv3_bf16(const void* X, int ldx, const void* W_bf16, int n_img, int H, int W, int C, int stride, int mode,
                                  const float* scale, const float* shift, const void* gate, int ldg, int act, void* Y, int y_half,
                                  int ldy, void* stream) {
   int wp, rows, bands;
-  if (!img_conv_plan(n_img, H, W, C, stride, mode, wp, rows, bands)) return -4;
-  if ((ldx % (mode ? 4 : 8)) || ((((uintptr_t)X) | ((uintptr_t)W_bf16)) & 15) || (y_half ? ((ldy % 2) || (((uintptr_t)Y) & 3)) : 0)) return -4;
-  if (mode == 1 && (gate == nullptr || y_half)) return -4;
-  if ((long long)n_img * H * W * (ldx > ldy ? ldx : ldy) >= (1ll << 31)) return -4;
+  if (!img_conv_check(n_img, H, W, C, stride, mode, X, ldx, W_bf16, Y, y_half, ldy, wp, rows, bands)) return -4;
+  if (mode == 1 && gate == nullptr) return -4;                 // (a missing operand, not a shape the query rejects)
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* Wt = (const unsigned short*)W_bf16;
   const unsigned short* G = (const unsigned short*)gate;

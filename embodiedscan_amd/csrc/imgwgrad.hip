@@ -317,18 +317,28 @@ static bool rows_wgrad_plan(int n, int Cin, int Cout, int& ci, int& co, int& sli
   return true;
 }
 
+// the whole gate of both paths below: the operands' layout, alignment and 32-bit index range (a null pointer: a fresh buffer)
+static bool wgrad_operands_ok(long long rows, const void* Xh, int ldx, const float* dY, int ldy) {
+  if ((ldx % 8) || (ldy % 4) || ((((uintptr_t)Xh) | ((uintptr_t)dY)) & 15)) return false;
+  return rows * (ldx > ldy ? ldx : ldy) < (1ll << 31);
+}
+
+static bool rows_wgrad_check(int n, int Cin, int Cout, const void* Xh, int ldx, const float* dY, int ldy, int& ci, int& co, int& slices,
+                             int& rows) {
+  return rows_wgrad_plan(n, Cin, Cout, ci, co, slices, rows) && wgrad_operands_ok(n, Xh, ldx, dY, ldy);
+}
+
+// (for fresh contiguous operands; the launcher answers for the caller's own with -4)
 extern "C" size_t es_rows_wgrad1_workspace_floats(int n, int Cin, int Cout) {
   int ci, co, slices, rows;
-  if (!rows_wgrad_plan(n, Cin, Cout, ci, co, slices, rows)) return 0;
+  if (!rows_wgrad_check(n, Cin, Cout, nullptr, Cin, nullptr, Cout, ci, co, slices, rows)) return 0;
   return (size_t)slices * Cin * Cout;
 }
 
 extern "C" int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n, int Cin, int Cout, float* dW, int accumulate,
                                    float* ws, size_t ws_floats, void* stream) {
   int ci, co, slices, rows;
-  if (!rows_wgrad_plan(n, Cin, Cout, ci, co, slices, rows)) return -4;
-  if ((ldx % 8) || (ldy % 4) || ((((uintptr_t)Xh) | ((uintptr_t)dY)) & 15)) return -4;
-  if ((long long)n * (ldx > ldy ? ldx : ldy) >= (1ll << 31)) return -4;
+  if (!rows_wgrad_check(n, Cin, Cout, Xh, ldx, dY, ldy, ci, co, slices, rows)) return -4;
   if (slices > 1 && (ws == nullptr || ws_floats < (size_t)slices * Cin * Cout)) return -5;
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* X = (const unsigned short*)Xh;
@@ -375,18 +385,21 @@ static bool img_wgrad_plan(int n_img, int H, int W, int C, int stride, int& wp, 
   return true;
 }
 
+static bool img_wgrad_check(int n_img, int H, int W, int C, int stride, const void* Xh, int ldx, const float* dY, int ldy, int& wp,
+                            int& rows, int& bands) {
+  return img_wgrad_plan(n_img, H, W, C, stride, wp, rows, bands) && wgrad_operands_ok((long long)n_img * H * W, Xh, ldx, dY, ldy);
+}
+
 extern "C" size_t es_img_wgrad9_workspace_floats(int n_img, int H, int W, int C, int stride) {
   int wp, rows, bands;
-  if (!img_wgrad_plan(n_img, H, W, C, stride, wp, rows, bands)) return 0;
+  if (!img_wgrad_check(n_img, H, W, C, stride, nullptr, C, nullptr, C, wp, rows, bands)) return 0;
   return (size_t)n_img * bands * 9 * C * C;
 }
 
 extern "C" int es_img_wgrad9_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n_img, int H, int W, int C, int stride,
                                   float* dW, int accumulate, float* ws, size_t ws_floats, void* stream) {
   int wp, rows, bands;
-  if (!img_wgrad_plan(n_img, H, W, C, stride, wp, rows, bands)) return -4;
-  if ((ldx % 8) || (ldy % 4) || ((((uintptr_t)Xh) | ((uintptr_t)dY)) & 15)) return -4;
-  if ((long long)n_img * H * W * (ldx > ldy ? ldx : ldy) >= (1ll << 31)) return -4;
+  if (!img_wgrad_check(n_img, H, W, C, stride, Xh, ldx, dY, ldy, wp, rows, bands)) return -4;
   const int parts = n_img * bands;
   if (parts > 1 && (ws == nullptr || ws_floats < (size_t)parts * 9 * C * C)) return -5;
   hipStream_t st = (hipStream_t)stream;

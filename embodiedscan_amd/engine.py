@@ -136,14 +136,8 @@ def _build_cast_table(dev):
     return tab
 
 
-PRECISION = ['f32']       # 'f32': exact-f32 MFMA everywhere; 'bf16': bf16 MFMA (f32 accumulate) for conv fwd / dgrad
-SHADOW = [os.environ.get('ES_SHADOW', '1') == '1']   # gather from bf16 shadow copies of activations / gradients: half the
-                          # gather bytes, no conversion instructions in the staging loop; on by default since round 2 (the GPU
-                          # suite passes identically with it; ES_SHADOW=0 restores f32 gathers)
-WGRAD_BF16 = [True]       # in bf16 mode also run the weight-gradient GEMMs on the bf16 matrix cores
-ACT16 = [os.environ.get('ES_ACT16', '1') != '0']   # round 3: the image backbone stores its ACTIVATIONS in bf16 (bf16 mode only):
-                          # the fused conv + frozen-BN (+ residual) + ReLU launches read and write bf16 rows, the data
-                          # gradients stay f32; halves the bytes of the HBM-bound 1x1 convolutions, no shadow copies
+PRECISION = ['f32']       # 'f32': exact-f32 MFMA everywhere; 'bf16': bf16 MFMA (f32 accumulate) for conv fwd / dgrad / wgrad;
+                          # the gathers read bf16 shadow copies of activations / gradients where the fast kernel takes the shape
 WEIGHT_VERSION = [0]      # bumped by the optimiser: invalidates the bf16 weight copies
 
 
@@ -301,16 +295,22 @@ _WGRAD_STREAMS = {}     # compute-stream handle -> dict(s=torch Stream, h=handle
 _KEEP = []              # temporaries read by queued weight-gradient launches; released by the final join
 
 
-def _wgrad_stream(*keep):
-    """handle of the weight-gradient stream of the current compute stream, made to wait for everything queued on the
-    compute stream so far; `keep`: tensors the launch reads that nobody else references."""
-    if not WGRAD_ASYNC[0]:
-        return _stream()
+def _wgrad_rec():
+    """the weight-gradient stream record of the current compute stream (created on first use)"""
     h = _stream()
     ws = _WGRAD_STREAMS.get(h)
     if ws is None:
         st = torch.cuda.Stream()
         ws = _WGRAD_STREAMS[h] = dict(s=st, h=st.cuda_stream, fork=torch.cuda.Event(), join=torch.cuda.Event(), used=False)
+    return ws
+
+
+def _wgrad_stream(*keep):
+    """handle of the weight-gradient stream of the current compute stream, made to wait for everything queued on the
+    compute stream so far; `keep`: tensors the launch reads that nobody else references."""
+    if not WGRAD_ASYNC[0]:
+        return _stream()
+    ws = _wgrad_rec()
     ws['fork'].record(hip.stream_obj())
     ws['s'].wait_event(ws['fork'])
     ws['used'] = True
@@ -318,86 +318,12 @@ def _wgrad_stream(*keep):
     return ws['h']
 
 
-_WGRAD_WS = {}          # stream handle -> persistent workspace of the deterministic weight-gradient row split
-# The first weight-gradient launch a weight receives in a step OVERWRITES its slot of the gradient arena (a plain store: the
-# read-modify-write of a 1 GB gradient made the wide occupancy layers wait on 128 dependent loads per thread); later launches of
-# the same step (shared modules, the 8 taps of a transposed convolution have their own slots) accumulate.  Keyed by the slot's
-# device pointer, so aliases of one tensor share the stamp.  new_grad_epoch() is called where the arena is zeroed.
-GRAD_EPOCH = [1]
-_GRAD_STAMP = {}
-WGRAD_OVERWRITE = [os.environ.get('ES_WGRAD_OVERWRITE', '1') != '0']
-
-
-def new_grad_epoch():
-    GRAD_EPOCH[0] += 1
-    if len(_GRAD_STAMP) > 1 << 16:
-        _GRAD_STAMP.clear()
-
-
-def _first_write(ptr):
-    """0 (overwrite) for the first gradient written to `ptr` in this epoch, 1 (accumulate) afterwards"""
-    if not WGRAD_OVERWRITE[0]:
-        return 1
-    acc = 1 if _GRAD_STAMP.get(ptr) == GRAD_EPOCH[0] else 0
-    _GRAD_STAMP[ptr] = GRAD_EPOCH[0]
-    return acc
-
-
-def _wgrad(name, sw, dW, *args):
-    """launch a weight-gradient entry point (`args` = everything between the function name and dW) on stream `sw` with the
-    workspace its row split asks for.  One buffer per stream, grown on demand and reused by every launch of that stream:
-    the launches of a stream (partial tiles -> fixed-order reduction into dW) are ordered, so the reuse is race free."""
-    if name == 'es_spconv_wgrad_bf16_src':
-        X, xh, ldx, dY, yh, ldy, nbr, n_out, n_in, K, cin, cout = args
-        need = hip.raw('es_spconv_wgrad_workspace_floats')(1, X, xh, ldx, dY, yh, ldy, n_out, n_in, K, cin, cout)
-    else:
-        X, ldx, dY, ldy, nbr, n_out, n_in, K, cin, cout = args
-        need = hip.raw('es_spconv_wgrad_workspace_floats')(int(name == 'es_spconv_wgrad_bf16'), X, 0, ldx, dY, 0, ldy, n_out, n_in,
-                                                           K, cin, cout)
-    ws = None
-    if need:
-        ws = _WGRAD_WS.get(sw)
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _KEEP.append(ws)                 # launches already queued on `sw` may still use the old buffer
-            ws = _WGRAD_WS[sw] = torch.empty(max(int(need), 1 << 22), dtype=torch.float32, device=torch.device('cuda', torch.cuda.current_device()))
-    call(name, *args, dW, _first_write(dW), P(ws), ws.numel() if ws is not None else 0, sw)
-
-
-IMG_WGRAD = [os.environ.get('ES_IMG_WGRAD', '1') != '0']     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
-ROWS_WGRAD = [os.environ.get('ES_ROWS_WGRAD', '1') != '0']   # round 6: 1x1 weight gradients on contiguous rows (streaming kernel of csrc/imgwgrad.hip)
-IMG_CONV = [os.environ.get('ES_IMG_CONV', '1') != '0']       # round 6: 3x3 image forward / gated data gradient on csrc/imgconv.hip
-
-
-def _img_wgrad_floats(img, K, cin, cout, x, gy):
-    """workspace floats of the image weight-gradient kernel for this launch, 0 when it does not take it: `img` = (n_img, H, W, stride)
-    of a 3x3 / pad 1 convolution on image rows ((H, W) = its INPUT grid); bf16 activation rows, f32 gradient rows, C -> C channels
-    (32 / 64), stride 1 or 2"""
-    if not (IMG_WGRAD[0] and img is not None and K == 9 and cin == cout and x.dh is not None and gy.dtype == torch.float32):
-        return 0
-    return int(hip.raw('es_img_wgrad9_workspace_floats')(img[0], img[1], img[2], cin, img[3]))
-
-
-def _img_wgrad(sw, dW, xh, ldx, gy, ldy, img, C, need):
-    ws = _WGRAD_WS.get(sw)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _KEEP.append(ws)                     # launches already queued on `sw` may still use the old buffer
-        ws = _WGRAD_WS[sw] = torch.empty(max(int(need), 1 << 22), dtype=torch.float32, device=gy.device)
-    call('es_img_wgrad9_bf16', P(xh), ldx, P(gy), ldy, img[0], img[1], img[2], C, img[3], dW, _first_write(dW), P(ws), ws.numel(), sw)
-
-
 def wgrad_stream_obj():
     """the torch Stream that carries the weight-gradient launches of the current compute stream (created on first use) -- idle during
     the forward pass, so small independent forward-time work (the grounder's frozen text encoder) can ride on it instead of opening
     one more stream: a process has four hardware queues, and a fifth, sixth ... stream ends up sharing one with a stream it was meant to
     overlap (bench.py copy_stream: ~ 10 - 18 % per step when that happens)"""
-    h = _stream()
-    ws = _WGRAD_STREAMS.get(h)
-    if ws is None:
-        st = torch.cuda.Stream()
-        ws = _WGRAD_STREAMS[h] = dict(s=st, h=st.cuda_stream, fork=torch.cuda.Event(), join=torch.cuda.Event(), used=False)
-    return ws['s']
+    return _wgrad_rec()['s']
 
 
 def join_wgrad_streams(final=True):
@@ -413,21 +339,81 @@ def join_wgrad_streams(final=True):
         _KEEP.clear()
 
 
-_TICKET_WS = {}         # stream handle -> zero-initialised f32 workspace of the last-block reductions queued on that stream
+# ------------------------------------------------------------------ per-stream workspaces
+# One buffer per (tag, stream), grown on demand and reused by every launch of that stream that names the tag: the launches of a
+# stream are ordered, so the reuse is race free.  Scratch tags: 'wgrad' (partial tensors of the weight-gradient row splits), 'dense'
+# (partial tiles of split dense launches).  Zeroed tags -- kernels that reduce per-workgroup partials in their last workgroup
+# (csrc/common.h es_last_block) keep a ticket counter at the head that is 0 before and after every launch: 'ticket', 'split', 'colsum'
+# and 'topk' (es_topk_mask_ws also keeps its selection state there).
+_ZEROED = ('ticket', 'split', 'colsum', 'topk')
+_WS = {tag: {} for tag in ('wgrad', 'dense') + _ZEROED}      # tag -> {stream handle: tensor}
+_WGRAD_WS = _WS['wgrad']
 
 
-def ticket_ws(floats, like, tag=''):
-    """(tensor, floats) workspace for a kernel that reduces per-workgroup partials in its last workgroup (csrc/common.h
-    es_last_block): its head holds a ticket counter that must be 0 before every launch and is left 0 by every launch, so ONE
-    zero-initialised buffer per stream serves all such launches of the stream (they are ordered); grown on demand.  `tag`: a
-    kernel family that leaves more than the ticket behind (es_topk_mask_ws keeps its selection state there) gets a buffer of its own."""
-    h = (_stream(), tag)
-    ws = _TICKET_WS.get(h)
-    if ws is None or ws.numel() < floats or ws.device != like.device:
+def stream_ws(stream, tag, floats, like):
+    """(tensor, floats): the f32 workspace `tag` of stream handle `stream`, at least `floats` long, on like.device"""
+    table = _WS[tag]
+    ws = table.get(stream)
+    if ws is None or ws.numel() < floats or ws.device != like.device:     # (a buffer of another device is never handed out)
         if ws is not None:
-            _KEEP.append(ws)                     # launches already queued may still use the old buffer
-        ws = _TICKET_WS[h] = torch.zeros(max(int(floats), 1 << 16), dtype=torch.float32, device=like.device)
+            _KEEP.append(ws)                     # launches already queued on `stream` may still use the old buffer
+        if tag in _ZEROED:
+            ws = torch.zeros(max(int(floats), 1 << 16), dtype=torch.float32, device=like.device)
+            if stream != _stream():              # the zero fill was queued on the current stream: order it before the first launch
+                ev = torch.cuda.Event()          # on `stream` that reads the ticket
+                ev.record(hip.stream_obj())
+                hip._stream_of(stream).wait_event(ev)
+        else:
+            ws = torch.empty(max(int(floats), 1 << 22), dtype=torch.float32, device=like.device)
+        table[stream] = ws
     return ws, ws.numel()
+
+
+def ticket_ws(floats, like, tag='ticket'):
+    """zero-initialised workspace of a last-block reduction on the current stream (see stream_ws)"""
+    assert tag in _ZEROED, tag
+    return stream_ws(_stream(), tag, floats, like)
+
+
+# The first weight-gradient launch a weight receives in a step OVERWRITES its slot of the gradient arena (a plain store: the
+# read-modify-write of a 1 GB gradient made the wide occupancy layers wait on 128 dependent loads per thread); later launches of
+# the same step (shared modules, the 8 taps of a transposed convolution have their own slots) accumulate.  Keyed by the slot's
+# device pointer, so aliases of one tensor share the stamp.  new_grad_epoch() is called where the arena is zeroed.
+GRAD_EPOCH = [1]
+_GRAD_STAMP = {}
+
+
+def new_grad_epoch():
+    GRAD_EPOCH[0] += 1
+    if len(_GRAD_STAMP) > 1 << 16:
+        _GRAD_STAMP.clear()
+
+
+def _first_write(ptr):
+    """0 (overwrite) for the first gradient written to `ptr` in this epoch, 1 (accumulate) afterwards"""
+    acc = 1 if _GRAD_STAMP.get(ptr) == GRAD_EPOCH[0] else 0
+    _GRAD_STAMP[ptr] = GRAD_EPOCH[0]
+    return acc
+
+
+def _wgrad(name, sw, dW, *args, like=None, acc=None):
+    """launch a weight-gradient entry point (`args` = everything between the function name and dW) on stream `sw` with the
+    workspace its row split asks for (that stream's 'wgrad' buffer); like: a tensor on the launch's device (None: the current GPU,
+    for callers that hold raw pointers only); acc: the accumulate flag (None: _first_write(dW))"""
+    if name == 'es_spconv_wgrad_bf16_src':
+        X, xh, ldx, dY, yh, ldy, nbr, n_out, n_in, K, cin, cout = args
+        need = hip.raw('es_spconv_wgrad_workspace_floats')(1, X, xh, ldx, dY, yh, ldy, n_out, n_in, K, cin, cout)
+    else:
+        X, ldx, dY, ldy, nbr, n_out, n_in, K, cin, cout = args
+        need = hip.raw('es_spconv_wgrad_workspace_floats')(int(name == 'es_spconv_wgrad_bf16'), X, 0, ldx, dY, 0, ldy, n_out, n_in,
+                                                           K, cin, cout)
+    if like is None:
+        like = torch.empty(0, device=torch.device('cuda', torch.cuda.current_device()))
+    ws, nf = stream_ws(sw, 'wgrad', need, like) if need else (None, 0)
+    call(name, *args, dW, _first_write(dW) if acc is None else acc, P(ws), nf, sw)
+
+
+IMG_WGRAD = [os.environ.get('ES_IMG_WGRAD', '1') != '0']     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
 
 
 # Python's cyclic collector and the train loop (round 5, profiles/r5d / r5f_bench_grounding_diag.json: `gc_collections`): a generation-2
@@ -483,15 +469,15 @@ def reset_tickets():
     """re-zero the ticket heads of every cached election workspace (on the current stream).  A launch that faulted inside an
     in-launch reduction leaves its ticket non-zero; the step that saw the fault has already raised HipError, a caller that
     catches it and continues must call this (after synchronising) before the next step."""
-    for ws in _TICKET_WS.values():
-        ws[:min(ws.numel(), 2048)].zero_()
+    for tag in _ZEROED:
+        for ws in _WS[tag].values():
+            ws[:min(ws.numel(), 2048)].zero_()
 
 
 def drop_caches():
     """forget every per-stream workspace / kept temporary (tests that switch between devices or libraries in one process)"""
-    _TICKET_WS.clear()
-    _WGRAD_WS.clear()
-    _DC_WS.clear()
+    for table in _WS.values():
+        table.clear()
     _KEEP.clear()
 
 
@@ -529,9 +515,6 @@ def _cast_rows(t):
 
 GEN_FUSED = [os.environ.get('ES_GEN_FUSED', '1') != '0']          # generative transposed conv: 8 taps in one launch per direction (round 4:
                                                                   # run on hardware, forward bit-identical, step -0.6 ms; profiles/r4a_*)
-NORM_SHADOW = [os.environ.get('ES_NORM_SHADOW', '1') != '0']     # norm apply passes write the bf16 shadows of their outputs
-WGRAD_SHADOW = [os.environ.get('ES_WGRAD_SHADOW', '1') != '0']   # weight-gradient launches gather from the bf16 shadows too
-DET_SPLIT = [os.environ.get('ES_DET_SPLIT', '1') != '0']   # deterministic tap split (workspace + fixed-order reduction)
 
 
 def _split_ws(n_out, K, cin, cout, like):
@@ -539,7 +522,7 @@ def _split_ws(n_out, K, cin, cout, like):
     es_spconv_split_workspace_floats): (tensor or None, floats).  Its head holds the tile tickets of the in-kernel reduction (zero
     before and after every launch), so it is the stream's persistent zero-initialised ticket workspace (ticket_ws), not a fresh
     allocation: the split launches of a stream are ordered, each has read its partial tiles before the next one starts."""
-    if not DET_SPLIT[0] or K <= 1 or n_out <= 0:
+    if K <= 1 or n_out <= 0:
         return None, 0
     nf = int(hip.raw('es_spconv_split_workspace_floats')(n_out, K, cin, cout))
     if nf == 0:
@@ -595,8 +578,8 @@ def _halo_launch(Xh, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, ac
     taps mirrored (sparse.CoordSet.inverse_map marks it `_mirror_of`): such a data gradient runs on the forward map's plan."""
     fwd = getattr(nbr, '_mirror_of', None)
     loc, hrows, hcnt = halo_plan(fwd if fwd is not None else nbr)
-    call('es_spconv_halo_bf16', Xh, ldx, Wp, P(loc), P(hrows), P(hcnt), n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc,
-         int(fwd is not None), _stream())
+    return hip.try_call('es_spconv_halo_bf16', Xh, ldx, Wp, P(loc), P(hrows), P(hcnt), n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc,
+                        int(fwd is not None), _stream())
 
 
 def empty(shape, like, dtype=torch.float32):
@@ -629,7 +612,6 @@ def _grad_target(v, shape_like):
 # a callable returning (nbr, inv), so the maps of a layer the dense engine covers completely are never built.
 # Z = 0 names a FLAT grid: nn.Conv2d on (B, X, Y) images (the FPN's 3x3 output convolutions); a bias is pre-filled, the launch accumulates.
 DENSE = [os.environ.get('ES_DENSE', '1') != '0']
-_DC_WS = {}             # stream handle -> persistent workspace of the partial tiles of split dense launches
 
 
 def _dense_geom(dense):
@@ -637,47 +619,32 @@ def _dense_geom(dense):
 
 
 def dense_ok(dense, mode, cin, cout):
+    """the dense engine takes this shape (es_dconv_supported: for fresh contiguous operands -- the launch itself answers for the
+    caller's, _dense_launch / _dense_wgrad return False where it does not take them)"""
     if not (DENSE[0] and dense is not None and PRECISION[0] == 'bf16'):
         return False
     if mode == 2 and dense[4] == 1 and (cin // 256) * (cout // 256) < 48:
         # weight gradient of a 1x1x1 convolution: one workgroup per 256 x 256 channel tile walking every row -- the neck's 768 -> 1536
         # down-sample would launch 18 of them (134 us against the map kernel's row-split 49 us, profiles/r5p_occ_launches.jsonl)
         return False
-    # the library's own 32-bit index limits (rows x leading dimension, taps x channels^2: es_dconv_* return -4 beyond them) are part of
-    # the answer, so that such a shape falls back to the map kernels instead of raising; callers check contiguity
-    B, X, Y, Z, ks = dense[:5]
-    rows = B * X * Y * max(Z, 1) * (8 if mode >= 3 else 1)
-    taps = ks ** (2 if Z == 0 else 3)
-    if rows * max(cin, cout) >= (1 << 31) or taps * cin * cout >= (1 << 31):
-        return False
     return hip.raw('es_dconv_supported')(_dense_geom(dense), mode, cin, cout) == 1
-
-
-def _dense_ws(s, need, like):
-    """the partial-tile workspace of split dense launches on stream `s` (None when the launch needs none)"""
-    if not need:
-        return None
-    ws = _DC_WS.get(s)
-    if ws is None or ws.numel() < need or ws.device != like.device:
-        if ws is not None:
-            _KEEP.append(ws)                     # launches already queued on this stream may still use the old buffer
-        ws = _DC_WS[s] = torch.empty(max(need, 1 << 22), dtype=torch.float32, device=like.device)
-    return ws
 
 
 def _dense_launch(Xh, ldx, Wp, dense, mode, cin, cout, Y, ldy, acc, like):
     g = _dense_geom(dense)
     s = _stream()
-    ws = _dense_ws(s, int(hip.raw('es_dconv_workspace_floats')(g, mode, cin, cout)), like)
-    call('es_dconv_fwd_bf16', Xh, ldx, Wp, g, mode, cin, cout, Y, ldy, acc, P(ws), ws.numel() if ws is not None else 0, s)
+    need = int(hip.raw('es_dconv_workspace_floats')(g, mode, cin, cout))
+    ws, nf = stream_ws(s, 'dense', need, like) if need else (None, 0)
+    return hip.try_call('es_dconv_fwd_bf16', Xh, ldx, Wp, g, mode, cin, cout, Y, ldy, acc, P(ws), nf, s)
 
 
 def _dense_wgrad(xh, ldx, gh, ldy, dense, transposed, cin, cout, dW, acc, sw, like):
     """weight gradient on the dense engine, on the weight-gradient stream `sw`; launches of few tiles over many rows (the 2-D 3x3
     layers) slice the rows through that stream's workspace"""
     g = _dense_geom(dense)
-    ws = _dense_ws(sw, int(hip.raw('es_dconv_wgrad_workspace_floats')(g, transposed, cin, cout)), like)
-    call('es_dconv_wgrad_ws_bf16', xh, ldx, gh, ldy, g, transposed, cin, cout, dW, acc, P(ws), ws.numel() if ws is not None else 0, sw)
+    need = int(hip.raw('es_dconv_wgrad_workspace_floats')(g, transposed, cin, cout))
+    ws, nf = stream_ws(sw, 'dense', need, like) if need else (None, 0)
+    return hip.try_call('es_dconv_wgrad_ws_bf16', xh, ldx, gh, ldy, g, transposed, cin, cout, dW, acc, P(ws), nf, sw)
 
 
 class _Maps:
@@ -704,29 +671,28 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     bf = PRECISION[0] == 'bf16' and cin >= 16
     if maps is not None:
         maps = _Maps(maps) if not isinstance(maps, _Maps) else maps
-    x16 = x.d.dtype == torch.bfloat16                  # bf16 activation rows (the image backbone's outputs under ACT16): their own shadow
+    x16 = x.d.dtype == torch.bfloat16                  # bf16 activation rows (the image backbone's outputs): their own shadow
     if x16:
         assert bf and _ld(x.d) == cin, 'bf16 input rows need the bf16 kernels and contiguous rows'
         x.dh = x.d
-    dn = dense if (bf and _ld(x.d) == cin and dense_ok(dense, 0, cin, cout)) else None
-    if dn is None and maps is not None:
-        nbr, inv = maps.get()
-    if dn is not None:
-        if bias:                                  # rows pre-filled with the bias, the launch accumulates (the tile's accumulators fill the
-            y.d.copy_(bias.d.expand_as(y.d))      # register file: an epilogue that also held the bias spilled)
-        _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dn, 0, cin, cout, P(y.d), cout, 1 if bias else 0, x.d)
-    elif bf and (x16 or (SHADOW[0] and _ld(x.d) == cin and _use_shadow(n_in, cin, K, cin, cout))):
-        if _halo_ok(nbr, n_out, n_in, cin, K, cin, cout):
-            _halo_launch(P(x.shadow()), cin, P(w.bf16()[1]), nbr, n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d), cout, 0)
-        else:
-            _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
+    dn = bf and _ld(x.d) == cin and dense_ok(dense, 0, cin, cout)
+    if dn and bias:                               # rows pre-filled with the bias, the launch accumulates (the tile's accumulators fill the
+        y.d.copy_(bias.d.expand_as(y.d))          # register file: an epilogue that also held the bias spilled)
+    if not (dn and _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 0, cin, cout, P(y.d), cout, 1 if bias else 0, x.d)):
+        if maps is not None:
+            nbr, inv = maps.get()
+        if bf and (x16 or (_ld(x.d) == cin and _use_shadow(n_in, cin, K, cin, cout))):
+            if not (_halo_ok(nbr, n_out, n_in, cin, K, cin, cout)
+                    and _halo_launch(P(x.shadow()), cin, P(w.bf16()[1]), nbr, n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
+                                     cout, 0)):
+                _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
+                          cout, 0, x.d)
+        elif bf:
+            _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
                       cout, 0, x.d)
-    elif bf:
-        _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
-                  cout, 0, x.d)
-    else:
-        call('es_spconv_fwd', P(x.d), _ld(x.d), P(w.d), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
-             P(y.d), cout, 0, 0, _stream())
+        else:
+            call('es_spconv_fwd', P(x.d), _ld(x.d), P(w.d), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
+                 P(y.d), cout, 0, 0, _stream())
 
     def bwd():
         if y.g is None:
@@ -745,11 +711,9 @@ def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, g
     gate: folded-BN scale of x's producer -- the dgrad launch then also applies that layer's ReLU mask and BN scale
     (x is its only consumer), leaving x.g as the gradient of the producer's raw conv output."""
     K, cin, cout = w.d.shape
-    n_in = x.d.shape[0]
-    s = _stream()
     rec = None
     # dense engine: weight gradient / data gradient by address arithmetic where the library takes the shape
-    dn_ok = bf and dense is not None and gate is None and _ld(gy) == cout and _ld(x.d) == cin and WGRAD_BF16[0]
+    dn_ok = bf and dense is not None and gate is None and _ld(gy) == cout and _ld(x.d) == cin
     dn_w = dense if (dn_ok and w.g is not None and dense_ok(dense, 2, cin, cout)) else None
     dn_d = dense if (dn_ok and need_dx and x.rg and dense_ok(dense, 1, cin, cout)) else None
     if maps is not None and (DEBUG_CONV is not None or (w.g is not None and dn_w is None) or (need_dx and x.rg and dn_d is None)):
@@ -762,83 +726,100 @@ def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, g
     # the forward pass, of the weight-gradient launch (made here, before the weight-gradient stream forks)
     gh = None
     if dn_w is not None or dn_d is not None or (
-            bf and cout >= 16 and SHADOW[0] and need_dx and x.rg and gate is None and _ld(gy) == cout
-            and _use_shadow(n_out, cout, K, cout, cin)):
+            bf and cout >= 16 and need_dx and x.rg and gate is None and _ld(gy) == cout and _use_shadow(n_out, cout, K, cout, cin)):
         gh = y.grad_shadow() if gy is y.g else _cast_rows(gy)
     if dn_w is not None:
         x.shadow()                               # (made by the forward launch; never on the weight-gradient stream)
     if w.g is not None or (bias is not None and bias.g is not None):
         sw = _wgrad_stream(gy, x.d, gh, x.dh)
-    iw = _img_wgrad_floats(img, K, cin, cout, x, gy) if (w.g is not None and bf and dn_w is None) else 0
-    # 1x1 layers on contiguous rows (identity map), bf16 activation rows, f32 gradient rows: streaming kernel (csrc/imgwgrad.hip)
-    rw = 0
-    if (w.g is not None and bf and dn_w is None and not iw and ROWS_WGRAD[0] and K == 1 and nbr is None and n_in == n_out
-            and x.dh is not None and gy.dtype == torch.float32):
-        rw = int(hip.raw('es_rows_wgrad1_workspace_floats')(n_out, cin, cout))
-    if dn_w is not None:
-        _dense_wgrad(P(x.dh), cin, P(gh), cout, dn_w, 0, cin, cout, P(w.g), _first_write(P(w.g)), sw, gh)
-    elif iw:
-        _img_wgrad(sw, P(w.g), x.dh, _ld(x.dh), gy, _ld(gy), img, cin, iw)
-    elif rw:
-        ws = _WGRAD_WS.get(sw)
-        if ws is None or ws.numel() < rw:
-            if ws is not None:
-                _KEEP.append(ws)
-            ws = _WGRAD_WS[sw] = torch.empty(max(rw, 1 << 22), dtype=torch.float32, device=gy.device)
-        call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g), _first_write(P(w.g)), P(ws), ws.numel(), sw)
-    elif w.g is not None and bf and WGRAD_BF16[0] and ((SHADOW[0] and WGRAD_SHADOW[0] and (gh is not None or x.dh is not None))
-                                                  or x.d.dtype == torch.bfloat16):      # (bf16 activation rows ARE their shadow: ES_SHADOW=0 must not strand them)
-        xs, ys = x.dh if x.dh is not None else x.d, gh if gh is not None else gy
-        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), int(gh is not None), _ld(ys),
-               P(nbr), n_out, n_in, K, cin, cout)
-    elif w.g is not None:
-        assert x.d.dtype == torch.float32, 'bf16 activation rows reach the weight gradient through their shadow (x.dh)'
-        _wgrad('es_spconv_wgrad_bf16' if (bf and WGRAD_BF16[0]) else 'es_spconv_wgrad', sw, P(w.g), P(x.d), _ld(x.d), P(gy),
-               _ld(gy), P(nbr), n_out, n_in, K, cin, cout)
+    if w.g is not None:
+        _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw)
     if bias is not None and bias.g is not None:
         # column sums of gy (round 4: one deterministic launch on the weight-gradient stream; was an f32 GEMM against a column of ones)
         nb, dst = cout - bias_from, bias.g.data_ptr() + 4 * bias_from
-        key = (sw, 'colsum')
-        ws = _TICKET_WS.get(key)
-        need = int(hip.raw('es_colsum_workspace_floats')(n_out, nb))
-        if ws is None or ws.numel() < need or ws.device != gy.device:      # (a cached buffer of another device is never handed out)
-            if ws is not None:
-                _KEEP.append(ws)
-            ws = _TICKET_WS[key] = torch.zeros(max(need, 1 << 16), dtype=torch.float32, device=gy.device)
-            if sw != _stream():                  # the zero fill was queued on the compute stream, AFTER the weight-gradient stream forked:
-                ev = torch.cuda.Event()          # order the fill before the first launch that reads the ticket
-                ev.record(hip.stream_obj())
-                hip._stream_of(sw).wait_event(ev)
-        call('es_colsum', gy.data_ptr() + 4 * bias_from, _ld(gy), n_out, nb, dst, _first_write(dst), P(ws), ws.numel(), sw)
-    if need_dx and x.rg and gate is not None:
+        ws, nf = stream_ws(sw, 'colsum', int(hip.raw('es_colsum_workspace_floats')(n_out, nb)), gy)
+        call('es_colsum', gy.data_ptr() + 4 * bias_from, _ld(gy), n_out, nb, dst, _first_write(dst), P(ws), nf, sw)
+    if need_dx and x.rg:
+        _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img)
+    if rec is not None and rec['need_dx']:
+        rec['after'] = x.g.clone()               # (gradient buffer after this launch; `before` = what it accumulated onto)
+
+
+def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw):
+    """the weight-gradient launch of a convolution on stream `sw`: the first candidate that takes it (a fast path's launcher has the
+    last word on the operands: -4 passes on to the next candidate)"""
+    K, cin, cout = w.d.shape
+    n_in = x.d.shape[0]
+    acc = _first_write(P(w.g))
+    xh_f32 = bf and x.dh is not None and gy.dtype == torch.float32      # bf16 activation rows against f32 gradient rows
+    if dn_w is not None:                         # dense engine (dense_ok)
+        if _dense_wgrad(P(x.dh), cin, P(gh), cout, dn_w, 0, cin, cout, P(w.g), acc, sw, gh):
+            return
+        if maps is not None:                     # the maps are built on the compute stream: fork the weight-gradient stream again
+            nbr, _ = maps.get()
+            sw = _wgrad_stream()
+    # 3x3 / pad 1 image layers, C -> C channels, by address arithmetic on the image grid (csrc/imgwgrad.hip)
+    if IMG_WGRAD[0] and xh_f32 and img is not None and K == 9 and cin == cout:
+        nf = int(hip.raw('es_img_wgrad9_workspace_floats')(img[0], img[1], img[2], cin, img[3]))
+        if nf:
+            ws, nf = stream_ws(sw, 'wgrad', nf, gy)
+            if hip.try_call('es_img_wgrad9_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), img[0], img[1], img[2], cin, img[3], P(w.g), acc,
+                            P(ws), nf, sw):
+                return
+    # 1x1 layers on contiguous rows (identity map): streaming kernel (csrc/imgwgrad.hip)
+    if xh_f32 and K == 1 and nbr is None and n_in == n_out:
+        nf = int(hip.raw('es_rows_wgrad1_workspace_floats')(n_out, cin, cout))
+        if nf:
+            ws, nf = stream_ws(sw, 'wgrad', nf, gy)
+            if hip.try_call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g), acc, P(ws), nf, sw):
+                return
+    # map kernels: gathering from the bf16 shadows where they exist (bf16 activation rows are their own shadow)
+    if bf and (gh is not None or x.dh is not None or x.d.dtype == torch.bfloat16):
+        xs, ys = x.dh if x.dh is not None else x.d, gh if gh is not None else gy
+        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), int(gh is not None), _ld(ys),
+               P(nbr), n_out, n_in, K, cin, cout, like=gy, acc=acc)
+        return
+    assert x.d.dtype == torch.float32, 'bf16 activation rows reach the weight gradient through their shadow (x.dh)'
+    _wgrad('es_spconv_wgrad_bf16' if bf else 'es_spconv_wgrad', sw, P(w.g), P(x.d), _ld(x.d), P(gy), _ld(gy), P(nbr), n_out, n_in, K,
+           cin, cout, like=gy, acc=acc)
+
+
+def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
+    """the data-gradient launch of a convolution into x.g: the first candidate that takes it (as _conv_wgrad).  gate: see _conv_backward"""
+    K, cin, cout = w.d.shape
+    n_in = x.d.shape[0]
+    s = _stream()
+    if gate is not None:
         assert x.g is None and bf, 'gated dgrad: x must have exactly one consumer'
         x.g, x.gated = torch.empty(x.d.shape, dtype=torch.float32, device=x.d.device), True
-        if (IMG_CONV[0] and img is not None and K == 9 and img[3] == 1 and cin == cout and x.d.dtype == torch.bfloat16
-                and gy.dtype == torch.float32 and _ld(x.d) == cin
-                and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, 1, 1) == 1):
-            # gated data gradient of a 3x3 image layer by address arithmetic (csrc/imgconv.hip, mode 1)
-            call('es_img_conv3_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, 1, 1, P(gate), 0, P(x.d), _ld(x.d), 3,
-                 P(x.g), 0, _ld(x.g), s)
-        elif x.d.dtype == torch.bfloat16:        # the gate operand is the bf16 activation (only its sign is read)
+        # 3x3 image layer by address arithmetic (csrc/imgconv.hip, mode 1)
+        if (img is not None and K == 9 and img[3] == 1 and cin == cout and x.d.dtype == torch.bfloat16 and gy.dtype == torch.float32
+                and _ld(x.d) == cin and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, 1, 1) == 1
+                and hip.try_call('es_img_conv3_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, 1, 1, P(gate), 0, P(x.d),
+                                 _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)):
+            return
+        if x.d.dtype == torch.bfloat16:          # the gate operand is the bf16 activation (only its sign is read)
             call('es_spconv_fwd_bf16_io', P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
                  P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
         else:
             call('es_spconv_fwd_bf16_affine', P(gy), _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
                  P(x.d), _ld(x.d), 3, P(x.g), _ld(x.g), s)
-    elif need_dx and x.rg:
-        g, acc = _grad_target(x, x.d)
-        if dn_d is not None:
-            _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(g), _ld(g), acc, gh)
-        elif gh is not None and _halo_ok(inv, n_in, n_out, cout, K, cout, cin):
-            _halo_launch(P(gh), cout, P(w.bf16()[0]), inv, n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc)
-        elif gh is not None:
-            _fwd_bf16(P(gh), 1, cout, P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gh)
-        elif bf and cout >= 16:
-            _fwd_bf16(P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gy)
-        else:
-            call('es_spconv_fwd', P(gy), _ld(gy), P(w.d), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), 1, acc, s)
-    if rec is not None and rec['need_dx']:
-        rec['after'] = x.g.clone()               # (gradient buffer after this launch; `before` = what it accumulated onto)
+        return
+    g, acc = _grad_target(x, x.d)
+    if dn_d is not None:                         # dense engine (dense_ok)
+        if _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(g), _ld(g), acc, gh):
+            return
+        if maps is not None:
+            _, inv = maps.get()
+    if gh is not None and _halo_ok(inv, n_in, n_out, cout, K, cout, cin) and \
+            _halo_launch(P(gh), cout, P(w.bf16()[0]), inv, n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc):
+        return
+    if gh is not None:
+        _fwd_bf16(P(gh), 1, cout, P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gh)
+    elif bf and cout >= 16:
+        _fwd_bf16(P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gy)
+    else:
+        call('es_spconv_fwd', P(gy), _ld(gy), P(w.d), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), 1, acc, s)
 
 
 def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=True, sole_consumer=False, out_bf16=False, img=None):
@@ -846,7 +827,7 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
     fused into the conv epilogue); in f32 mode conv() followed by affine_act().
     sole_consumer: promise that x feeds nothing but this conv; if x itself came out of a fused conv+BN+ReLU, its
     ReLU/BN backward is then folded into this conv's data-gradient launch.
-    out_bf16: store the output rows in bf16 (ACT16); x / res may themselves be bf16 row matrices.
+    out_bf16: store the output rows in bf16 (the image backbone's activations); x / res may themselves be bf16 row matrices.
     img: (n_img, H, W, stride) when the map is a 3x3 / pad 1 image-grid map: the weight gradient may then run by address arithmetic
     (csrc/imgwgrad.hip) instead of through the map."""
     K, cin, cout = w.d.shape
@@ -854,15 +835,15 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
     if PRECISION[0] != 'bf16':
         return affine_act(conv(x, w, nbr, inv, n_out, need_dx=need_dx), scale, shift, act=act, res=res)
     h16 = torch.bfloat16
-    y16 = bool(out_bf16 and ACT16[0] and cout % 4 == 0)
+    y16 = bool(out_bf16 and cout % 4 == 0)
     x16, r16 = x.d.dtype == h16, (res is not None and res.d.dtype == h16)
     y = Var(empty((n_out, cout), x.d, dtype=h16 if y16 else torch.float32))
     # round 6: 3x3 layers on an image grid by address arithmetic (csrc/imgconv.hip) where the library takes the shape
-    ic = (IMG_CONV[0] and img is not None and K == 9 and x16 and res is None and act in (0, 1) and cin == cout and _ld(x.d) == cin
+    ic = (img is not None and K == 9 and x16 and res is None and act in (0, 1) and cin == cout and _ld(x.d) == cin
           and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, img[3], 0) == 1)
-    if ic:
-        call('es_img_conv3_bf16', P(x.d), cin, P(w.bf16()[1]), img[0], img[1], img[2], cin, img[3], 0, P(scale), P(shift), 0, 0, act,
-             P(y.d), int(y16), cout, _stream())
+    if ic and hip.try_call('es_img_conv3_bf16', P(x.d), cin, P(w.bf16()[1]), img[0], img[1], img[2], cin, img[3], 0, P(scale), P(shift), 0,
+                           0, act, P(y.d), int(y16), cout, _stream()):
+        pass                                    # (-4: the launcher did not take the operands -- the map kernels below)
     elif x16 or r16 or y16:
         call('es_spconv_fwd_bf16_io', P(x.d), int(x16), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale),
              P(shift), P(res.d) if res is not None else 0, int(r16), _ld(res.d) if res is not None else 0, act, P(y.d),
@@ -936,8 +917,8 @@ def gen_conv_transpose(x, w):
         for k in range(8):
             gy = y.g.data_ptr() + 4 * k * cout
             if w.g is not None:
-                _wgrad('es_spconv_wgrad_bf16' if (bf and WGRAD_BF16[0]) else 'es_spconv_wgrad', sw,
-                       w.g.data_ptr() + 4 * k * cin * cout, P(x.d), _ld(x.d), gy, 8 * cout, 0, n, n, 1, cin, cout)
+                _wgrad('es_spconv_wgrad_bf16' if bf else 'es_spconv_wgrad', sw,
+                       w.g.data_ptr() + 4 * k * cin * cout, P(x.d), _ld(x.d), gy, 8 * cout, 0, n, n, 1, cin, cout, like=y.g)
             if dfused:
                 continue
             if g is not None and bf:
@@ -952,6 +933,11 @@ def gen_conv_transpose(x, w):
     return y
 
 
+def _required(taken):
+    if not taken:
+        raise hip.HipError('the dense engine did not take the operands of a launch that has no other path (status -4)')
+
+
 def conv_transpose_dense(x, w, dense):
     """nn.ConvTranspose3d(k=2, s=2) on a dense (B, X, Y, Z) grid (dense = (B, X, Y, Z, 2, 2, 0)): y (B*2X*2Y*2Z, Cout) in DENSE row order
     by the parity-class launch of the dense engine (csrc/dconv.hip mode 3) -- no generative-layout intermediate, no row permutation;
@@ -959,7 +945,7 @@ def conv_transpose_dense(x, w, dense):
     K, cin, cout = w.d.shape
     n = x.d.shape[0]
     y = Var(empty((n * 8, cout), x.d))
-    _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 3, cin, cout, P(y.d), cout, 0, x.d)
+    _required(_dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 3, cin, cout, P(y.d), cout, 0, x.d))
 
     def bwd():
         if y.g is None:
@@ -969,10 +955,10 @@ def conv_transpose_dense(x, w, dense):
         if w.g is not None:
             x.shadow()
             sw = _wgrad_stream(y.g, x.d, gh, x.dh)
-            _dense_wgrad(P(x.dh), cin, P(gh), cout, dense, 1, cin, cout, P(w.g), _first_write(P(w.g)), sw, gh)
+            _required(_dense_wgrad(P(x.dh), cin, P(gh), cout, dense, 1, cin, cout, P(w.g), _first_write(P(w.g)), sw, gh))
         if x.rg:
             g, acc = _grad_target(x, x.d)
-            _dense_launch(P(gh), cout, P(w.bf16()[0]), dense, 4, cin, cout, P(g), _ld(g), acc, gh)
+            _required(_dense_launch(P(gh), cout, P(w.bf16()[0]), dense, 4, cin, cout, P(g), _ld(g), acc, gh))
         if DEBUG_CONV is not None:                     # the 8 taps as 8 identity-map K = 1 records sharing one data gradient (as gen_conv_transpose)
             B, X, Y, Z = dense[:4]
             gv = y.g.view(B, X, 2, Y, 2, Z, 2, cout)
@@ -1001,7 +987,7 @@ def norm(x, weight, bias, seg_off, eps, act=0, res=None, running=None, momentum=
     # bf16 mode: the apply passes also write the bf16 gather shadows their consumers would otherwise make with a cast launch
     # each (forward: of y, for the next convolution; backward: of the gradient handed to the producing convolution, when this
     # norm is that Var's only consumer) -- bit-identical to the casts they replace
-    fuse = NORM_SHADOW[0] and PRECISION[0] == 'bf16' and SHADOW[0] and C >= 16 and C % 8 == 0
+    fuse = PRECISION[0] == 'bf16' and C >= 16 and C % 8 == 0
     private, x.fresh = bool(x.fresh), False
     if fuse:
         y.dh = empty((n, C), x.d, dtype=torch.bfloat16)

@@ -92,7 +92,7 @@ def _stream_of(handle):
     return st
 
 
-def call(name, *args):
+def _launch(name, args):
     prof = PROFILE
     if prof is not None and name in prof['names']:
         e0, e1 = prof['event'](), prof['event']()
@@ -100,11 +100,26 @@ def call(name, *args):
         e0.record(st)
         rc = _fn[name](*args)
         e1.record(st)
-        prof['records'].append((name, e0, e1, args))          # bench.py resolves PAIRS[map pointer] right after
+        if rc == 0:
+            prof['records'].append((name, e0, e1, args))      # bench.py resolves PAIRS[map pointer] right after
     else:
         rc = _fn[name](*args)
+    return rc
+
+
+def call(name, *args):
+    rc = _launch(name, args)
     if rc != 0:
         raise HipError(f'{name} failed with status {rc}')
+
+
+def try_call(name, *args):
+    """call() for a fast path whose launcher has the last word on its operands (leading dimensions, alignment, 32-bit row indices):
+    False when it returns -4 -- nothing was launched, the caller takes its next candidate"""
+    rc = _launch(name, args)
+    if rc not in (0, -4):
+        raise HipError(f'{name} failed with status {rc}')
+    return rc == 0
 
 
 def raw(name):

@@ -96,7 +96,7 @@ class ResNet:
         """x: (n_img, H, W, 3) f32 channels-last.  Returns [(Var (n_img*h*w, C), h, w)] for the out_indices."""
         n_img, H, W, _ = x.shape
         dev = x.device
-        a16 = bool(self.act16 and E.ACT16[0] and E.PRECISION[0] == 'bf16' and self.frozen_stages >= 0)
+        a16 = bool(self.act16 and E.PRECISION[0] == 'bf16' and self.frozen_stages >= 0)
         fused = self.base in (16, 32, 64) and self.frozen_stages >= 0 and a16 and STEM_POOL[0]     # stem + max pool in one launch
         direct = (self.base in (16, 32) and self.frozen_stages >= 0) or fused
         key = (n_img, H, W, direct)
@@ -186,6 +186,6 @@ class ResNet:
         # the table-driven bf16 weight cast must run OUTSIDE the captured sequence (inside, capture would stamp every kernel as
         # cast without executing the launch, and every replay would redo it): bring the copies up to date first
         E.refresh_weight_copies()
-        key = (x.data_ptr(), tuple(x.shape), E.PRECISION[0], bool(self.act16 and E.ACT16[0]), E.TAPE.enabled, self._fold_version,
-               self.arena.data.data_ptr(), E.SHADOW[0], E.WGRAD_SHADOW[0], E.IMG_CONV[0])
+        key = (x.data_ptr(), tuple(x.shape), E.PRECISION[0], bool(self.act16), E.TAPE.enabled, self._fold_version,
+               self.arena.data.data_ptr())
         return E.graphed(self._graphs, key, lambda: self.forward(x))

@@ -469,7 +469,9 @@ int es_topk_sorted(const float* vals, int B, int L, const int* vlen_dev, int k, 
  * accumulate 1: Y += result.  Launches that would leave the chip under-filled split their reduction over several workgroups
  * per tile; the partial tiles go through `ws` (es_dconv_workspace_floats; 0 = not needed) and are added in slice order
  * (bit-reproducible).  -4: shape not taken (es_dconv_supported: reduction channels % 64, result channels % 128 -- 256-column tiles where they
- * divide, 128-column tiles for the neck's 128-channel out blocks; weight gradients (modes 2 / 5): both % 256). */
+ * divide, 128-column tiles for the neck's 128-channel out blocks; weight gradients (modes 2 / 5): both % 256).  es_dconv_supported answers for
+ * fresh contiguous operands; the launchers apply the same check to the operands they are given (leading dimensions, 16-byte pointers,
+ * 32-bit row indices) and return -4, launching nothing, where it fails -- the caller then takes the map kernels. */
 int es_dconv_supported(const int* geom_host, int mode, int Cin, int Cout);
 size_t es_dconv_workspace_floats(const int* geom_host, int mode, int Cin, int Cout);
 int es_dconv_fwd_bf16(const void* Xh, int ldx, const void* W_bf16, const int* geom_host, int mode, int Cin, int Cout, float* Y,
@@ -508,7 +510,8 @@ int es_dconv_set_option(int key, int value);
  *   gradient of a stride-1 convolution on ONE coordinate set (its inverse map is the forward map with the taps mirrored:
  *   inv[i][k] == nbr[i][26 - k]) runs on the FORWARD map's plan, no second plan is built.
  * es_spconv_halo_supported: 1 when the shape is taken AND the launch fills the chip (>= `min workgroups`, es_halo_set_option 30;
- *   smaller launches belong to the tap-split gather kernels). */
+ *   smaller launches belong to the tap-split gather kernels) for fresh source rows; es_spconv_halo_bf16 applies the same check to the
+ *   rows it is given and returns -4, launching nothing, where it fails. */
 size_t es_halo_plan_rows(int n_out);
 int es_halo_plan(const int* nbr, int n_out, int K, void* loc, int* hrows, int* hcnt, void* stream);
 int es_halo_set_option(int key, int value);
@@ -522,7 +525,8 @@ int es_spconv_halo_bf16(const void* Xh, int ldx, const void* W_bf16, const void*
  * (configs/detection/mv-det3d_8xb4_embodiedscan-3d-284class-9dof.py:24-34): Xh (n_img*H*W x ldx) bf16 activation rows, dY
  * (n_img*H*W x ldy) f32 rows of the output gradient (rounded to bf16 in the kernel), taps t = ty*3 + tx with the neighbour
  * (stride*y + ty - 1, stride*x + tx - 1) -- es_image_map's order.  Takes C = 32 with output width <= 128 (64 for stride 2) and C = 64 with <= 64 (the w16 backbone's
- * layer2 / layer3); es_img_wgrad9_workspace_floats returns 0 for any other shape (the caller keeps the map kernel) and -4 / -5
+ * layer2 / layer3); es_img_wgrad9_workspace_floats returns 0 for any other shape (the caller keeps the map kernel; it answers for fresh
+ * contiguous operands -- the launcher applies the same check to the ones it is given) and -4 / -5
  * are returned for an unsupported shape / a workspace that is too small.  Partial tensors per workgroup are added in workgroup
  * order: bit-reproducible.  es_img_wgrad_set_option: 40 on / off, 41 / 42 workgroups aimed for at C = 32 / 64. */
 size_t es_img_wgrad9_workspace_floats(int n_img, int H, int W, int C, int stride);
@@ -545,7 +549,8 @@ int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n
  *   shift[c]) on the (H/stride, W/stride) output grid, bf16 rows (y_half 1) or f32; stride 1 or 2 (even H, W); act 0 / 1 (ReLU);
  * mode 1 gated data gradient of a stride-1 layer: X = f32 rows of the output gradient, W_bf16 = the natural [9][Cin][Cout] copy,
  *   gate (n_img*H*W x ldg) = the layer input's bf16 activation rows, Y (f32) = (gate > 0) ? (X * W^T, taps mirrored) * scale[c] : 0.
- * es_img_conv3_supported: 1 when the shape is taken (C = 16: output width <= 128, stride 1; 32: <= 64; 64: <= 32); -4 otherwise.
+ * es_img_conv3_supported: 1 when the shape is taken (C = 16: output width <= 128, stride 1; 32: <= 64; 64: <= 32) with fresh contiguous
+ *   operands, 0 otherwise; es_img_conv3_bf16 applies the same check to the operands it is given and returns -4, launching nothing, where it fails.
  * es_img_conv_set_option: 50 on / off, 51 workgroups aimed for. */
 int es_img_conv3_supported(int n_img, int H, int W, int C, int stride, int mode);
 int es_img_conv3_bf16(const void* X, int ldx, const void* W_bf16, int n_img, int H, int W, int C, int stride, int mode,

@@ -534,3 +534,66 @@ def test_engine_fpn_output_convolution_dense_equals_image_map_path(emulated, mon
     for a, b_, name in zip(res[True], res[False], ('y', 'dx', 'dw', 'db')):
         err = float((a - b_).abs().max() / b_.abs().max())
         assert err < 2e-5, (name, err)
+
+
+def test_dense_launchers_refuse_operands_the_query_cannot_see(emu):
+    """es_dconv_supported answers for fresh contiguous operands -- the 32-bit row-index limit included -- and es_dconv_fwd_bf16 /
+    es_dconv_wgrad_ws_bf16 apply the same check to the operands they are given: a leading dimension off by 4 or a pointer 8 bytes off a
+    16-byte boundary returns -4 without a launch (the engine then takes the map kernels)"""
+    sup = emu.fns['es_dconv_supported']
+    cin = cout = 256
+    g = _geom(1, 6, 5, 4, 3, 1, 1)
+    buf = np.zeros(1 << 20, np.float32)
+    a = (P(buf) + 15) // 16 * 16                                   # a 16-byte aligned operand inside buf
+    for mode, lda, ldb in ((0, cin, cout), (1, cout, cin), (2, cin, cout)):
+        assert sup(P(g), mode, cin, cout) == 1
+        bad_ldb = ldb + (4 if mode == 2 else 2)                    # (bf16 rows: ld % 8; f32 result rows: ld % 4)
+        for A, la, B, lb in ((a, lda + 4, a, ldb), (a, lda, a, bad_ldb), (a + 8, lda, a, ldb), (a, lda, a + 8, ldb)):
+            if mode == 2:
+                rc = emu.fns['es_dconv_wgrad_ws_bf16'](A, la, B, lb, P(g), 0, cin, cout, a, 0, a, 1 << 18, 0)
+            else:
+                rc = emu.fns['es_dconv_fwd_bf16'](A, la, a, P(g), mode, cin, cout, B, lb, 0, a, 1 << 18, 0)
+            assert rc == -4, (mode, A - a, la, B - a, lb, rc)
+    big = _geom(1, 160, 160, 160, 3, 1, 1)                          # 4.1 M rows: rows x 1024 channels >= 2^31 (query only: never launched)
+    assert sup(P(big), 0, 256, 256) == 1 and sup(P(big), 0, 1024, 256) == 0
+
+
+def test_engine_dense_falls_back_for_a_misaligned_gradient(emulated, monkeypatch):
+    """an existing input gradient 8 bytes off a 16-byte boundary: the dense data gradient is not taken (es_dconv_supported sees the
+    result operand) and the call equals the same call with the dense engine off"""
+    import torch
+    from embodiedscan_amd import engine as E, hip
+    from embodiedscan_amd.models.necks.imvoxel_neck import VolumeGrid
+    dev = emulated
+    monkeypatch.setitem(_ListAsDict(E.PRECISION), 0, 'bf16')
+    gen = torch.Generator().manual_seed(12)
+    B, X, Y, Z, cin, cout = 1, 5, 4, 4, 256, 256
+    grid = VolumeGrid(B, X, Y, Z, dev)
+    n = B * X * Y * Z
+    xd = torch.randn(n, cin, generator=gen)
+    wd = torch.randn(27, cin, cout, generator=gen) / (27 * cin) ** 0.5
+    gy = torch.randn(n, cout, generator=gen)
+    res = {}
+    for dense_on in (True, False):
+        monkeypatch.setitem(_ListAsDict(E.DENSE), 0, dense_on)
+        x = E.Var(xd.clone())
+        store = torch.ones(n * cin + 4)
+        x.g = store[2:2 + n * cin].view(n, cin)                     # 8 bytes off
+        assert x.g.data_ptr() % 16 == 8
+        w = E.Param(wd.clone(), torch.zeros_like(wd))
+        w.bf_n, w.bf_t = torch.empty((27, cin, cout), dtype=torch.bfloat16), torch.empty((27, cout, cin), dtype=torch.bfloat16)
+        hip.call('es_cast_weight_bf16', hip.P(w.d), 27, cin, cout, hip.P(w.bf_n), hip.P(w.bf_t), 0)
+        w.bf_step = E.WEIGHT_VERSION[0]
+        E.TAPE.clear()
+        E.new_grad_epoch()
+        _launch_log()
+        y = E.conv(x, w, None, None, n, dense=(B, X, Y, Z, 3, 1, 1), maps=lambda: grid.conv_map(3, 1, 1)[:2])
+        y.g = gy.clone()
+        E.TAPE.backward()
+        log = _launch_log()
+        assert ('k_dconv<' in log) == dense_on, log                  # (the forward still runs on the dense engine)
+        res[dense_on] = (y.d.clone(), x.g.clone(), w.g.clone())
+    for a, b, name in zip(res[True], res[False], ('y', 'dx', 'dw')):
+        err = float((a - b).abs().max() / b.abs().max())
+        assert err < 2e-5, (name, err)
+    assert torch.equal(res[True][1], res[False][1])                  # (both data gradients ran on the map kernel)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from test_emu_kernels import P, _conv_ref, bf16_bits, bf16_round, emu  # noqa: F401  (the fixture)
+from test_emu_product import emulated  # noqa: F401  (the fixture that puts the product's host layer on the emulator)
 
 K = 27
 
@@ -180,3 +181,58 @@ def test_halo_empty_rows_and_support_rule(emu):
     x = np.zeros((4, 64), np.uint16)
     rc = emu.fns['es_spconv_halo_bf16'](P(x), 64, P(x), P(x), P(x), P(x), 4, 4, 27, 32, 128, 0, P(x), 128, 0, 0, 0)
     assert rc == -4
+
+
+def test_halo_launcher_refuses_misaligned_source_rows(emu):
+    """es_spconv_halo_supported answers for fresh source rows; es_spconv_halo_bf16 applies the same check to the rows it is given: 8 bytes
+    off a 16-byte boundary returns -4 without a launch (the engine then takes the gather kernels)"""
+    buf = np.zeros(1 << 12, np.float32)
+    a = (P(buf) + 15) // 16 * 16
+    assert emu.fns['es_spconv_halo_supported'](370000, 370000, 128, K, 128, 128) == 1
+    assert emu.fns['es_spconv_halo_bf16'](a + 8, 128, a, a, a, a, 370000, 370000, K, 128, 128, 0, a, 128, 0, 0, 0) == -4
+
+
+def test_engine_halo_falls_back_for_misaligned_source_rows(emulated, monkeypatch):
+    """engine.conv on bf16 activation rows 8 bytes off a 16-byte boundary: the halo kernel is not taken and the forward equals the
+    same call with the halo path off (the tap-split gather kernel on the same operands)"""
+    import torch
+    from embodiedscan_amd import engine as E, hip
+    from test_emu_product import _ListAsDict
+    monkeypatch.setitem(_ListAsDict(E.PRECISION), 0, 'bf16')
+    rng = np.random.default_rng(31)
+    n, cin, cout = 600, 64, 128
+    nbr = torch.from_numpy(_local_map(rng, n, n, 0.6))
+    gen = torch.Generator().manual_seed(31)
+    xd = torch.randn(n, cin, generator=gen).to(torch.bfloat16)
+    wd = torch.randn(K, cin, cout, generator=gen) / (K * cin) ** 0.5
+    store = torch.zeros(n * cin + 8, dtype=torch.bfloat16)
+    off = store[4:4 + n * cin].view(n, cin)                          # 8 bytes off
+    off.copy_(xd)
+    assert off.data_ptr() % 16 == 8
+    hip.raw('es_halo_set_option')(30, 1)                             # (take launches of any size)
+    try:
+        res = {}
+        for name, halo_on, x in (('aligned', True, xd.clone()), ('off', True, off), ('halo off', False, off)):
+            monkeypatch.setitem(_ListAsDict(E.HALO), 0, halo_on)
+            w = E.Param(wd.clone(), torch.zeros_like(wd))
+            w.bf_n, w.bf_t = torch.empty((K, cin, cout), dtype=torch.bfloat16), torch.empty((K, cout, cin), dtype=torch.bfloat16)
+            hip.call('es_cast_weight_bf16', hip.P(w.d), K, cin, cout, hip.P(w.bf_n), hip.P(w.bf_t), 0)
+            w.bf_step = E.WEIGHT_VERSION[0]
+            E.TAPE.clear()
+            _launch_log()
+            res[name] = E.conv(E.Var(x, rg=False), w, nbr, None, n).d.clone()
+            assert ('k_spconv_halo' in _launch_log()) == (name == 'aligned'), name
+        E.TAPE.clear()
+    finally:
+        hip.raw('es_halo_set_option')(30, 192)
+    assert torch.equal(res['off'], res['halo off'])
+    assert float((res['aligned'] - res['halo off']).abs().max() / res['halo off'].abs().max()) < 2e-5
+
+
+def _launch_log():
+    import ctypes
+    import build as emu_build
+    lib = ctypes.CDLL(emu_build.build())
+    buf = ctypes.create_string_buffer(1 << 16)
+    lib.es_emu_take_launch_log(buf, len(buf))
+    return buf.value.decode()

@@ -130,3 +130,16 @@ def test_stem_and_max_pool_in_one_launch(emu):
         got = np.full((n_img * Hp * Wp, C), 0xffff, np.uint16)
         emu('es_stem_pool_fwd', P(x), P(w), P(scale), P(shift), n_img, H, W, C, P(got), 0)
         assert np.array_equal(got, want), (n_img, H, W, C, int((got != want).sum()))
+
+
+def test_image_convolution_launcher_refuses_operands_the_query_cannot_see(emu):
+    """es_img_conv3_supported answers for fresh contiguous operands -- the 32-bit row-index limit included -- and es_img_conv3_bf16
+    applies the same check to the operands it is given: a leading dimension off by 4, an input 8 bytes off a 16-byte boundary or an odd
+    bf16 output leading dimension returns -4 without a launch"""
+    sup = emu.fns['es_img_conv3_supported']
+    buf = np.zeros(1 << 12, np.float32)
+    a = (P(buf) + 15) // 16 * 16
+    assert sup(80, 60, 60, 32, 1, 0) == 1 and sup(80, 60, 60, 32, 1, 1) == 1
+    for mode, x, ldx, y_half, ldy in ((0, a, 36, 1, 32), (0, a + 8, 32, 1, 32), (0, a, 32, 1, 33), (1, a, 34, 0, 32), (1, a + 8, 32, 0, 32)):
+        assert emu.fns['es_img_conv3_bf16'](x, ldx, a, 80, 60, 60, 32, 1, mode, a, a, a, 32, 1, a, y_half, ldy, 0) == -4, (mode, x - a, ldx)
+    assert sup(16384, 32, 32, 64, 1, 0) == 1 and sup(65536, 32, 32, 64, 1, 0) == 0      # 2^26 rows x 64 channels >= 2^31

@@ -112,3 +112,116 @@ def test_rows_weight_gradient_of_1x1_layers(emu, lazy):
     finally:
         emu.lib.es_emu_set_dma_mode(0)
         emu('es_img_wgrad_set_option', 43, 500000)
+
+
+def test_weight_gradient_launchers_refuse_operands_the_queries_cannot_see(emu):
+    """es_img_wgrad9_workspace_floats / es_rows_wgrad1_workspace_floats answer for fresh contiguous operands -- the 32-bit row-index limit
+    included -- and the launchers apply the same check to the operands they are given: a leading dimension off by 4 or a pointer 8 bytes
+    off a 16-byte boundary returns -4 without a launch (the engine then takes the map kernel)"""
+    buf = np.zeros(1 << 12, np.float32)
+    a = (P(buf) + 15) // 16 * 16
+    img, rows = emu.fns['es_img_wgrad9_workspace_floats'], emu.fns['es_rows_wgrad1_workspace_floats']
+    assert img(80, 60, 60, 32, 1) > 0 and rows(18000, 256, 512) > 0
+    for x, ldx, dy, ldy in ((a, 36, a, 32), (a, 32, a, 34), (a + 8, 32, a, 32), (a, 32, a + 8, 32)):
+        assert emu.fns['es_img_wgrad9_bf16'](x, ldx, dy, ldy, 80, 60, 60, 32, 1, a, 0, a, 1 << 30, 0) == -4, (x - a, ldx, dy - a, ldy)
+    for x, ldx, dy, ldy in ((a, 260, a, 512), (a, 256, a, 514), (a + 8, 256, a, 512), (a, 256, a + 8, 512)):
+        assert emu.fns['es_rows_wgrad1_bf16'](x, ldx, dy, ldy, 18000, 256, 512, a, 0, a, 1 << 30, 0) == -4, (x - a, ldx, dy - a, ldy)
+    assert img(16384, 32, 32, 64, 1) > 0 and img(65536, 32, 32, 64, 1) == 0             # 2^26 rows x 64 channels >= 2^31
+    assert rows(4000000, 512, 512) > 0 and rows(5000000, 512, 512) == 0
+
+
+from test_emu_product import emulated, _ListAsDict  # noqa: E402,F401  (the fixture that puts the product's host layer on the emulator)
+from test_emu_halo import _launch_log  # noqa: E402
+
+
+def _bf16_param(wd):
+    import torch
+    from embodiedscan_amd import engine as E, hip
+    K, cin, cout = wd.shape
+    w = E.Param(wd.clone(), torch.zeros_like(wd))
+    w.bf_n, w.bf_t = torch.empty((K, cin, cout), dtype=torch.bfloat16), torch.empty((K, cout, cin), dtype=torch.bfloat16)
+    hip.call('es_cast_weight_bf16', hip.P(w.d), K, cin, cout, hip.P(w.bf_n), hip.P(w.bf_t), 0)
+    w.bf_step = E.WEIGHT_VERSION[0]
+    return w
+
+
+def _off8(t):
+    """a copy of row matrix t 8 bytes off a 16-byte boundary"""
+    import torch
+    e = 8 // t.element_size()
+    store = torch.zeros(t.numel() + 2 * e, dtype=t.dtype)
+    v = store[e:e + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 8
+    return v
+
+
+def test_engine_image_layer_falls_back_for_misaligned_activation_rows(emulated, monkeypatch):
+    """engine.conv_affine(img=...) on bf16 activation rows 8 bytes off a 16-byte boundary: neither the image convolution nor the image weight
+    gradient is taken, and forward and weight gradient equal the same call with both paths off (library options 50 / 40)"""
+    import torch
+    from embodiedscan_amd import engine as E, hip
+    monkeypatch.setitem(_ListAsDict(E.PRECISION), 0, 'bf16')
+    n_img, H, W, C = 2, 8, 8, 32
+    n = n_img * H * W
+    gen = torch.Generator().manual_seed(21)
+    xd = torch.randn(n, C, generator=gen).to(torch.bfloat16)
+    wd = torch.randn(9, C, C, generator=gen) / (9 * C) ** 0.5
+    scale, shift = 0.5 + torch.rand(C, generator=gen), torch.randn(C, generator=gen)
+    gy = torch.randn(n, C, generator=gen)
+    nbr = torch.empty((n, 9), dtype=torch.int32)
+    hip.call('es_image_map', n_img, H, W, H, W, 3, 3, 1, 1, hip.P(nbr), 0)
+    res = {}
+    try:
+        for name, on, x in (('aligned', 1, xd.clone()), ('off', 1, _off8(xd)), ('paths off', 0, _off8(xd))):
+            hip.raw('es_img_conv_set_option')(50, on)
+            hip.raw('es_img_wgrad_set_option')(40, on)
+            w = _bf16_param(wd)
+            E.TAPE.clear()
+            E.new_grad_epoch()
+            _launch_log()
+            y = E.conv_affine(E.Var(x), w, nbr, None, n, scale, shift, act=1, need_dx=False, out_bf16=True, img=(n_img, H, W, 1))
+            y.g = gy.clone()
+            E.TAPE.backward()
+            log = _launch_log()
+            assert ('k_img_conv3' in log) == ('k_img_wgrad9' in log) == (name == 'aligned'), (name, log)
+            res[name] = (y.d.float(), w.g.clone())
+    finally:
+        hip.raw('es_img_conv_set_option')(50, 1)
+        hip.raw('es_img_wgrad_set_option')(40, 1)
+    for a, b in zip(res['off'], res['paths off']):
+        assert torch.equal(a, b)
+    for a, b, name in zip(res['aligned'], res['paths off'], ('y', 'dw')):
+        assert float((a - b).abs().max() / b.abs().max()) < 2e-2, name      # (bf16 output rows: one rounding apart at most)
+
+
+def test_engine_rows_weight_gradient_falls_back_for_a_misaligned_gradient(emulated, monkeypatch):
+    """the 1x1 weight gradient of engine.conv on contiguous bf16 rows with an output gradient 8 bytes off a 16-byte boundary: the streaming
+    kernel is not taken and the weight gradient equals the same call with that path off (library option 40)"""
+    import torch
+    from embodiedscan_amd import engine as E, hip
+    monkeypatch.setitem(_ListAsDict(E.PRECISION), 0, 'bf16')
+    n, cin, cout = 4096, 64, 64
+    gen = torch.Generator().manual_seed(22)
+    xd = torch.randn(n, cin, generator=gen).to(torch.bfloat16)
+    wd = torch.randn(1, cin, cout, generator=gen) / cin ** 0.5
+    gy = torch.randn(n, cout, generator=gen)
+    res = {}
+    hip.raw('es_img_wgrad_set_option')(43, 0)                        # (every width from 4 096 rows)
+    try:
+        for name, on, g in (('aligned', 1, gy.clone()), ('off', 1, _off8(gy)), ('path off', 0, _off8(gy))):
+            hip.raw('es_img_wgrad_set_option')(40, on)
+            w = _bf16_param(wd)
+            E.TAPE.clear()
+            E.new_grad_epoch()
+            _launch_log()
+            y = E.conv(E.Var(xd.clone()), w, None, None, n, need_dx=False)
+            y.g = g
+            E.TAPE.backward()
+            assert ('k_rows_wgrad1' in _launch_log()) == (name == 'aligned'), name
+            res[name] = w.g.clone()
+    finally:
+        hip.raw('es_img_wgrad_set_option')(40, 1)
+        hip.raw('es_img_wgrad_set_option')(43, 500000)
+    assert torch.equal(res['off'], res['path off'])
+    assert float((res['aligned'] - res['path off']).abs().max() / res['path off'].abs().max()) < 2e-5

@@ -45,7 +45,6 @@ def emulate():
     torch.cuda.current_stream = lambda *a, **k: stream
     from embodiedscan_amd import engine as E
     E.TWO_STREAMS[0] = E.WGRAD_ASYNC[0] = E.GRAPHS[0] = False          # the single-stream schedule
-    E._WGRAD_WS[0] = torch.empty(1 << 25, dtype=torch.float32)
     return torch.device('cpu')
 
 

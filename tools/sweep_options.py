@@ -76,7 +76,7 @@ def main():
             for k, v in kv:
                 if k.isdigit():                       # es_set_option key
                     hip.raw('es_set_option')(int(k), int(v))
-                else:                                 # engine flag (a one-element list), e.g. NORM_SHADOW=0, ACT16=0
+                else:                                 # engine flag (a one-element list), e.g. HALO=0, DENSE=0
                     old[k] = getattr(E, k)[0]
                     getattr(E, k)[0] = bool(int(v))
             run('options ' + var)
@@ -96,10 +96,6 @@ def main():
             hip.raw('es_set_option')(key, v)
             run(f'{names[key]} = {v} (default {defaults[key]})')
         hip.raw('es_set_option')(key, defaults[key])
-    for flag, lab in ((E.ACT16, 'bf16 activation storage OFF'), (E.WGRAD_OVERWRITE, 'first-write overwrite OFF')):
-        flag[0] = False
-        run(lab)
-        flag[0] = True
     run('default (last)')
 
 
