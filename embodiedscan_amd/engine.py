@@ -194,7 +194,8 @@ def graphed(cache, key, fn):
     shadows; 2nd: captured, then replayed).  Eager whenever per-launch instrumentation is on, on the default stream (capture
     needs a non-default stream: the side stream of the two-stream schedule), or after a failed capture."""
     global _NEW_VARS
-    instrumented = hip.PROFILE is not None or DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None
+    instrumented = (hip.PROFILE is not None or DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None
+                    or DEBUG_FWD is not None)
     if not GRAPHS[0] or instrumented or _NEW_VARS is not None or \
             torch.cuda.current_stream() == torch.cuda.default_stream():
         GRAPH_STATS['eager'] += 1
@@ -504,6 +505,28 @@ DEBUG_CONV = None       # tests/test_gpu_insitu.py sets a list: one record per c
                         # weight- / data-gradient launch against its arithmetic specification
 DEBUG_OPS = None        # ... and a list for the other backward launches with parameters or matrix-core arithmetic: attention
                         # (kind 'attn'), LayerNorm ('ln'), ContrastiveEmbed ('contrastive', appended by GroundingHead)
+DEBUG_FWD = None        # ... and for the forward launches (fwd_record): a list, or a callable that receives each record at once (a check
+                        # on the spot: nothing accumulates over a config-scale step)
+
+
+def fwd_record(kind, entry, **ops):
+    """DEBUG_FWD: one record of the forward launch that has just been queued -- `entry`: the entry point that took it; `ops`: its
+    operands and outputs, cloned here on the launch's stream (later in-place writers -- relu_, upsample_add_ -- cannot change them).
+    A Param / ParamSlice operand is recorded as its f32 values plus (`<name>_h`) the bf16 copy a bf16 launch read."""
+    rec = dict(kind=kind, entry=entry, precision=PRECISION[0])
+    for k, v in ops.items():
+        if isinstance(v, (Param, ParamSlice)):
+            rec[k] = v.d.clone()
+            if PRECISION[0] == 'bf16' and v.d.dim() == 3:
+                rec[k + '_h'] = v.bf16()[1].clone()
+        elif isinstance(v, torch.Tensor):
+            rec[k] = v.clone()
+        else:
+            rec[k] = v
+    if callable(DEBUG_FWD):
+        DEBUG_FWD(rec)
+    else:
+        DEBUG_FWD.append(rec)
 
 
 def _cast_rows(t):
@@ -531,12 +554,13 @@ def _split_ws(n_out, K, cin, cout, like):
 
 
 def _fwd_bf16(X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, like):
-    """es_spconv_fwd_bf16 with the deterministic-split workspace when the launch would split its tap list"""
+    """es_spconv_fwd_bf16 with the deterministic-split workspace when the launch would split its tap list -> the entry point taken"""
     ws, nf = _split_ws(n_out, K, cin, cout, like)
     if ws is not None:
         call('es_spconv_fwd_bf16_ws', X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, P(ws), nf, _stream())
-    else:
-        call('es_spconv_fwd_bf16', X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, _stream())
+        return 'es_spconv_fwd_bf16_ws'
+    call('es_spconv_fwd_bf16', X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, _stream())
+    return 'es_spconv_fwd_bf16'
 
 
 def _use_shadow(n_rows, C, K, cin, cout):
@@ -678,21 +702,34 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     dn = bf and _ld(x.d) == cin and dense_ok(dense, 0, cin, cout)
     if dn and bias:                               # rows pre-filled with the bias, the launch accumulates (the tile's accumulators fill the
         y.d.copy_(bias.d.expand_as(y.d))          # register file: an epilogue that also held the bias spilled)
-    if not (dn and _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 0, cin, cout, P(y.d), cout, 1 if bias else 0, x.d)):
+    gathered = True                                # the launch gathers x's bf16 shadow (False: the f32 rows)
+    if dn and _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 0, cin, cout, P(y.d), cout, 1 if bias else 0, x.d):
+        entry = 'es_dconv_fwd_bf16'
+    else:
         if maps is not None:
             nbr, inv = maps.get()
         if bf and (x16 or (_ld(x.d) == cin and _use_shadow(n_in, cin, K, cin, cout))):
-            if not (_halo_ok(nbr, n_out, n_in, cin, K, cin, cout)
+            if (_halo_ok(nbr, n_out, n_in, cin, K, cin, cout)
                     and _halo_launch(P(x.shadow()), cin, P(w.bf16()[1]), nbr, n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
                                      cout, 0)):
-                _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
-                          cout, 0, x.d)
+                entry = 'es_spconv_halo_bf16'
+            else:
+                entry = _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
+                                  P(y.d), cout, 0, x.d)
         elif bf:
-            _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
-                      cout, 0, x.d)
+            gathered = False
+            entry = _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
+                              cout, 0, x.d)
         else:
+            gathered = False
             call('es_spconv_fwd', P(x.d), _ld(x.d), P(w.d), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
                  P(y.d), cout, 0, 0, _stream())
+            entry = 'es_spconv_fwd'
+    if DEBUG_FWD is not None:
+        if maps is not None:
+            nbr, inv = maps.get()
+        fwd_record('conv', entry, x=x.d, xh=x.dh if gathered else None, w=w, nbr=nbr, n_out=n_out, bias=bias.d if bias else None,
+                   round=bool(bf), y=y.d)
 
     def bwd():
         if y.g is None:
@@ -843,18 +880,23 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
           and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, img[3], 0) == 1)
     if ic and hip.try_call('es_img_conv3_bf16', P(x.d), cin, P(w.bf16()[1]), img[0], img[1], img[2], cin, img[3], 0, P(scale), P(shift), 0,
                            0, act, P(y.d), int(y16), cout, _stream()):
-        pass                                    # (-4: the launcher did not take the operands -- the map kernels below)
+        entry = 'es_img_conv3_bf16'             # (-4: the launcher did not take the operands -- the map kernels below)
     elif x16 or r16 or y16:
         call('es_spconv_fwd_bf16_io', P(x.d), int(x16), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale),
              P(shift), P(res.d) if res is not None else 0, int(r16), _ld(res.d) if res is not None else 0, act, P(y.d),
              int(y16), cout, _stream())
+        entry = 'es_spconv_fwd_bf16_io'
     else:
         call('es_spconv_fwd_bf16_affine', P(x.d), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale),
              P(shift), P(res.d) if res is not None else 0, _ld(res.d) if res is not None else 0, act, P(y.d), cout, _stream())
+        entry = 'es_spconv_fwd_bf16_affine'
     if y16:
         y.dh = y.d                              # bf16 rows are their own gather shadow
     if x16:
         x.dh = x.d
+    if DEBUG_FWD is not None:
+        fwd_record('conv_affine', entry, x=x.d, w=w, nbr=nbr, n_out=n_out, round=True, scale=scale, shift=shift,
+                   res=res.d if res is not None else None, act=act, y=y.d)
 
     if act == 1 and res is None:
         y.gate = scale
@@ -898,6 +940,9 @@ def gen_conv_transpose(x, w):
         else:
             call('es_spconv_fwd', P(x.d), _ld(x.d), w.d.data_ptr() + 4 * k * cin * cout, 0, n, n, 1, cin, cout, 0,
                  y.d.data_ptr() + 4 * k * cout, 8 * cout, 0, 0, s)
+    if DEBUG_FWD is not None:
+        fwd_record('gen_transpose', 'es_gen_transpose_fwd_bf16' if fused else ('es_spconv_fwd_bf16' if bf else 'es_spconv_fwd'),
+                   x=x.d, w=w, round=bf, y=y.d)
 
     def bwd():
         if y.g is None:
@@ -946,6 +991,8 @@ def conv_transpose_dense(x, w, dense):
     n = x.d.shape[0]
     y = Var(empty((n * 8, cout), x.d))
     _required(_dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 3, cin, cout, P(y.d), cout, 0, x.d))
+    if DEBUG_FWD is not None:
+        fwd_record('transpose_dense', 'es_dconv_fwd_bf16', x=x.d, xh=x.dh, w=w, dense=tuple(dense), round=True, y=y.d)
 
     def bwd():
         if y.g is None:
@@ -991,9 +1038,14 @@ def norm(x, weight, bias, seg_off, eps, act=0, res=None, running=None, momentum=
     private, x.fresh = bool(x.fresh), False
     if fuse:
         y.dh = empty((n, C), x.d, dtype=torch.bfloat16)
+    run0 = (rm.clone(), rv.clone()) if (DEBUG_FWD is not None and rm is not None) else (None, None)
     call('es_norm_fwd', P(x.d), _ld(x.d), n, C, so, nseg, float(eps), P(weight.d), P(bias.d),
          P(res.d) if res is not None else 0, _ld(res.d) if res is not None else 0, act, P(rm), P(rv), float(momentum),
          P(mean), P(invstd), P(ws), P(y.d), C, P(y.dh) if fuse else 0, _stream())
+    if DEBUG_FWD is not None:
+        fwd_record('norm', 'es_norm_fwd', x=x.d, w=weight.d, b=bias.d, seg_off=list(seg_off), eps=float(eps), act=act,
+                   res=res.d if res is not None else None, rm0=run0[0], rv0=run0[1], rm1=rm, rv1=rv, momentum=float(momentum),
+                   mean=mean, invstd=invstd, y=y.d, yh=y.dh if fuse else None)
 
     def bwd():
         if y.g is None:
@@ -1025,6 +1077,9 @@ def affine_act(x, scale, shift, act=1, res=None, need_dx=True):
     y = Var(empty((n, C), x.d))
     call('es_affine_act_fwd', P(x.d), P(scale), P(shift), P(res.d) if res is not None else 0, n, C, act, P(y.d),
          _stream())
+    if DEBUG_FWD is not None:
+        fwd_record('affine_act', 'es_affine_act_fwd', x=x.d, scale=scale, shift=shift, res=res.d if res is not None else None,
+                   act=act, y=y.d)
 
     def bwd():
         if y.g is None:
@@ -1049,6 +1104,8 @@ def maxpool(x, nbr, n_out, need_dx=True):
     y = Var(empty((n_out, C), x.d))
     arg = empty((n_out, C), x.d, torch.int32)
     call('es_maxpool_fwd', P(x.d), _ld(x.d), P(nbr), n_out, K, C, P(y.d), P(arg), _stream())
+    if DEBUG_FWD is not None:
+        fwd_record('maxpool', 'es_maxpool_fwd', x=x.d, nbr=nbr, y=y.d, arg=arg)
 
     def bwd():
         if y.g is None or not (need_dx and x.rg):
@@ -1193,6 +1250,9 @@ def layernorm(x, w, b, res=None, eps=1e-5):
     mean, rstd = empty((n,), x.d), empty((n,), x.d)
     call('es_layernorm_fwd', P(x.d), P(res.d) if res is not None else 0, n, C, P(w.d), P(b.d), float(eps), P(y.d),
          P(z) if res is not None else 0, P(mean), P(rstd), _stream())
+    if DEBUG_FWD is not None:
+        fwd_record('layernorm', 'es_layernorm_fwd', x=x.d, res=res.d if res is not None else None, w=w.d, b=b.d, eps=float(eps), y=y.d,
+                   z=z if res is not None else None, mean=mean, rstd=rstd)
 
     def bwd():
         if y.g is None:
@@ -1228,6 +1288,8 @@ def attention(q, k, v, B, H, Lq, Lk, klen=None):
     lse = empty((B * H * Lq,), q.d)
     call('es_attn_fwd', P(q.d), _ld(q.d), P(k.d), _ld(k.d), P(v.d), _ld(v.d), B, H, Lq, Lk, P(klen), P(o.d), H * 32, P(lse), bf,
          _stream())
+    if DEBUG_FWD is not None:
+        fwd_record('attention', 'es_attn_fwd', q=q.d, k=k.d, v=v.d, B=B, H=H, Lq=Lq, Lk=Lk, klen=klen, bf=bf, o=o.d, lse=lse)
 
     def bwd():
         if o.g is None:

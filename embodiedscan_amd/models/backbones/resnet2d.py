@@ -125,11 +125,17 @@ class ResNet:
             # round 6: stem + max pool in one launch, bf16 rows out (bit-identical to the pair below)
             yp = torch.empty((pool[2], self.base), dtype=torch.bfloat16, device=dev)
             call('es_stem_pool_fwd', P(xin), P(w1), P(self.fold['bn1'][0]), P(self.fold['bn1'][1]), n_img, H, W, self.base, P(yp), s)
+            if E.DEBUG_FWD is not None:
+                E.fwd_record('stem', 'es_stem_pool_fwd', x=xin, w=w1, scale=self.fold['bn1'][0], shift=self.fold['bn1'][1], n_img=n_img,
+                             H=H, W=W, pooled=True, y=yp)
             cur = None
         elif self.base in (16, 32) and self.frozen_stages >= 0:
             y = torch.empty((stem[2], self.base), dtype=torch.float32, device=dev)
             call('es_stem_conv_fwd', P(xin), P(w1), P(self.fold['bn1'][0]), P(self.fold['bn1'][1]), n_img, H, W,
                  self.base, P(y), s)
+            if E.DEBUG_FWD is not None:
+                E.fwd_record('stem', 'es_stem_conv_fwd', x=xin, w=w1, scale=self.fold['bn1'][0], shift=self.fold['bn1'][1], n_img=n_img,
+                             H=H, W=W, pooled=False, y=y)
             cur = E.Var(y, rg=False)
         else:                                   # generic engine: 49 taps as 27 + 22
             y = torch.empty((stem[2], self.base), dtype=torch.float32, device=dev)
@@ -144,6 +150,8 @@ class ResNet:
         elif a16:                               # frozen stem: forward-only pooling straight into bf16 rows
             yp = torch.empty((pool[2], self.base), dtype=torch.bfloat16, device=dev)
             call('es_maxpool_fwd_h', P(cur.d), self.base, P(pool[0]), pool[2], pool[0].shape[1], self.base, P(yp), s)
+            if E.DEBUG_FWD is not None:
+                E.fwd_record('maxpool', 'es_maxpool_fwd_h', x=cur.d, nbr=pool[0], y=yp, arg=None)
             cur = E.Var(yp, rg=False)
             cur.dh = yp
         else:

@@ -88,6 +88,9 @@ class GroundingHead:
         rowmax = torch.empty(B * L, dtype=torch.float32, device=dev) if want_max else None
         call('es_contrastive_fwd', P(visual.d), B, L, P(text.d), T, C, P(tlen), P(vlen), P(self.cls_bias.d),
              P(logits.d) if logits is not None else 0, T, P(rowmax), hip.stream())
+        if E.DEBUG_FWD is not None:
+            E.fwd_record('contrastive', 'es_contrastive_fwd', v=visual.d, text=text.d, B=B, L=L, T=T, tlen=tlen, vlen=vlen,
+                         bias=self.cls_bias.d, logits=logits.d if logits is not None else None, rowmax=rowmax)
         if logits is not None:
             def bwd():
                 if logits.g is None:

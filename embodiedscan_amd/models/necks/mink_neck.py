@@ -100,6 +100,9 @@ class MinkNeck:
             cls = torch.empty((n, self.num_classes), dtype=torch.float32, device=out.F.d.device)
             call('es_spconv_fwd', P(out.F.d), out.F.d.stride(0), P(self.cls_w), 0, n, n, 1, self.out_channels, self.num_classes,
                  P(self.cls_b), P(cls), self.num_classes, 0, 0, hip.stream())
+            if E.DEBUG_FWD is not None:
+                E.fwd_record('conv', 'es_spconv_fwd', x=out.F.d, xh=None, w=self.cls_w.view(1, self.out_channels, self.num_classes), nbr=None,
+                             n_out=n, bias=self.cls_b, round=False, y=cls)
             score = torch.empty(n, dtype=torch.float32, device=cls.device)
             call('es_row_max', P(cls), self.num_classes, n, self.num_classes, P(score), hip.stream())
             score_set = out.cs

@@ -1,10 +1,29 @@
 """3x3 image convolution kernels (csrc/imgconv.hip) on the GPU through the C ABI: forward (stride 1 / 2) and gated data gradient against
 the map-kernel path they replace (es_spconv_fwd_bf16_io on es_image_map / es_inverse_map: the oracle-pinned path of
-tests/test_gpu_resnet2d.py) on the same operands at the backbone's real shapes, run-to-run bit-identical."""
+tests/test_gpu_resnet2d.py) on the same operands at the backbone's real shapes, run-to-run bit-identical; and each of them against
+an independent f64 reference (torch conv2d / conv_transpose2d / max_pool2d in f64 on the GPU, on the bf16-rounded operands), element
+by element to the bound of tests/fwd_spec.py."""
+import math
+
 import pytest
 import torch
 
+import fwd_spec as FS
+
 pytestmark = pytest.mark.gpu
+
+
+def _nchw(rows, n_img, H, W):
+    return rows.double().view(n_img, H, W, -1).permute(0, 3, 1, 2)
+
+
+def _rows(t):
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+def _wk(w9):
+    """(9, Cin, Cout) taps in (ky, kx) order -> conv2d weight (Cout, Cin, 3, 3)"""
+    return w9.double().view(3, 3, w9.shape[1], w9.shape[2]).permute(3, 2, 0, 1)
 
 
 def _setup(n_img, H, W, C, S, seed=3):
@@ -48,6 +67,18 @@ def test_forward_vs_map_kernel(case):
     ulp = (y1.view(torch.int16).int() - y2.view(torch.int16).int()).abs()
     print(f'{case}: f32 rows vs map kernel {err:.2e} (tol 3e-6); bf16 rows differing by one ulp: {float((ulp > 0).float().mean()):.2e} (max {int(ulp.max())})')
     assert err < 3e-6 and int(ulp.max()) <= 1
+    import torch.nn.functional as F                           # independent reference: f64 conv2d on the bf16 operands
+    xr = _nchw(xh, n_img, H, W)
+    conv = _rows(F.conv2d(xr, _wk(wn), stride=S, padding=1))
+    A = _rows(F.conv2d(xr.abs(), _wk(wn).abs(), stride=S, padding=1))
+    sc, sh = scale.double()[None], shift.double()[None]
+    want = (sc * conv + sh).clamp(min=0)
+    lin = FS.U * math.sqrt(9 * C) * sc * A
+    stats = FS.Stats(f'image conv {case}')
+    rf = FS.bound_check(f'{case} f32 rows', yf, want, lin, sh.abs().expand_as(want), False, 'f32 rows', stats)[0]
+    FS.bound_check(f'{case} bf16 rows', y2, want, lin, sh.abs().expand_as(want), True, 'bf16 rows', stats)
+    assert bool((y2.double()[want < -FS.G * lin - FS.U * sh.abs()] == 0).all())
+    print(f'   vs f64 conv2d: worst |y - spec| / (u sqrt(9C) |scale| A) {rf:.3f} (bound {FS.G:g}); bf16 rows within one ulp')
 
 
 @pytest.mark.parametrize('case', [(20, 60, 60, 32), (20, 30, 30, 64), (3, 17, 45, 32)])
@@ -71,6 +102,14 @@ def test_gated_data_gradient_vs_map_kernel(case):
     err = float((d1 - d2).abs().max() / d1.abs().max())
     print(f'{case}: gated data gradient vs map kernel {err:.2e} (tol 3e-6); zero rows agree: {bool(((d1 == 0) == (d2 == 0)).all())}')
     assert err < 3e-6 and bool(((d1 == 0) == (d2 == 0)).all())
+    import torch.nn.functional as F                           # independent reference: f64 conv_transpose2d on the bf16 operands
+    gr = _nchw(gy.to(torch.bfloat16), n_img, H, W)
+    mask = (act.double() > 0) * scale.double()[None]
+    want = _rows(F.conv_transpose2d(gr, _wk(wn), padding=1)) * mask
+    A = _rows(F.conv_transpose2d(gr.abs(), _wk(wn).abs(), padding=1)) * mask.abs()
+    r = FS.bound_check(f'{case} gated data gradient', d2, want, FS.U * math.sqrt(9 * C) * A, torch.zeros_like(want), False, 'dgrad',
+                       FS.Stats('image conv'))[0]
+    print(f'   vs f64 conv_transpose2d: worst |d - spec| / (u sqrt(9C) A) {r:.3f} (bound {FS.G:g})')
 
 
 @pytest.mark.parametrize('case', [(20, 480, 640, 16), (3, 97, 131, 16), (2, 64, 64, 32), (10, 480, 640, 64)])
@@ -109,3 +148,10 @@ def test_stem_and_max_pool_in_one_launch(case):
         ts.append(e0.elapsed_time(e1) / 5 * 1e3)
     print(f'{case}: stem + pool as two launches {ts[0]:.1f} us, as one {ts[1]:.1f} us')
     assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+    # independent reference: f64 conv2d -> frozen BN -> ReLU -> max_pool2d, rounded to bf16 (tests/fwd_spec.py check_stem)
+    stats = FS.Stats(f'stem {case}')
+    FS.check_stem(dict(entry='es_stem_pool_fwd', x=x.view(-1, 3), w=w, scale=scale, shift=shift, n_img=n_img, H=H, W=W, pooled=True,
+                       y=got), dev, stats)
+    FS.check_stem(dict(entry='es_stem_conv_fwd', x=x.view(-1, 3), w=w, scale=scale, shift=shift, n_img=n_img, H=H, W=W, pooled=False,
+                       y=y), dev, stats)
+    print(stats.report())

@@ -25,12 +25,24 @@ Specifications (oracle/rounding.py restated on raw tensors; r = round-to-nearest
 Tolerance 2e-4 relative L2 per launch (only the f32 summation order -- and, for attention, the fast exponential flipping a
 few bf16 roundings -- is left; measured ~1e-6 .. 6e-5).  Small cases are specified on the host (CPU, f64); the config-4 /
 config-5 scale cases evaluate the same formulas with torch in f64 on the GPU (rocBLAS -- an implementation independent of the
-kernels under test), because the 3072^2 x 27 layers would take minutes on host cores."""
+kernels under test), because the 3072^2 x 27 layers would take minutes on host cores.
+
+The backward gate builds its specification from the forward's OUTPUTS, so it cannot see a forward defect.  engine.DEBUG_FWD therefore
+records every forward launch of the same step -- the entry point that took it, its operands and the bf16 shadows it gathered, its
+output cloned right after the launch -- and tests/fwd_spec.py holds each one to its f64 specification, per element (a relative L2
+over 10^5 rows would pass a few rows that are each 2 % off): convolution / Linear / transposed convolution and the fused epilogues
+to |y - spec| <= 8 u sqrt(n) (|scale| A + |bias|) + u (|shift| + |res|) (+ one bf16 ulp for bf16 rows), A the same gather-GEMM on
+absolute values; every shadow bit-exact.  Every test asserts which entry points it saw, so the gate cannot go quiet when a dispatch
+rule changes.  The backward checker gets the same per-element bound as an additional assertion: data gradients against A and what
+they accumulated onto, bias gradients per column against sqrt(rows) sum |gy| (the relative-L2 tolerance of a column sum that cancels
+-- the attention key-projection bias -- grows like 1 / |want| and passes anything)."""
 import os
 
 import numpy as np
 import pytest
 import torch
+
+import fwd_spec as FS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,10 +84,26 @@ def _spec(x, w, nbr, n_out, gy, round_fwd, round_dgrad, gate, xact):
     return dw, dx
 
 
+def _dx_bound(after, want, amag, before, n, label, tag, n_acc=1):
+    """per element (in addition to the relative L2 above): |after - want| <= G u sqrt(n) A + n_acc u |before|, A = the data gradient
+    of the same launch on absolute values -- no term depends on 1 / |want| -> the worst ratio |after - want| / (u sqrt(n) A)"""
+    err = (after - want).abs()
+    lin = FS.U * n ** 0.5 * amag
+    slack = n_acc * FS.U * before.abs() if before is not None else torch.zeros_like(err)
+    bound = FS.G * lin + slack
+    if bool((~(err <= bound)).any()):
+        i = int(torch.argmax((err - bound).reshape(-1)))
+        raise AssertionError(f'{label}: data gradient of {tag}: per-element bound exceeded at flat index {i}: |err| '
+                             f'{float(err.reshape(-1)[i]):.3e} > {float(bound.reshape(-1)[i]):.3e}')
+    pos = lin > 0
+    return float(((err - slack).clamp(min=0)[pos] / lin[pos]).max()) if bool(pos.any()) else 0.0
+
+
 def _check_conv_records(recs, label, dev):
     """every weight / bias / data gradient of the recorded convolution backwards against _spec; dev: where the
     specification is evaluated (cpu or the GPU, f64 either way)"""
     to = lambda t: None if t is None else t.to(dev)
+    ratio_dx = ratio_db = 0.0
     by_w, by_b = {}, {}
     for r in recs:
         if r['w'].g is not None:
@@ -99,15 +127,19 @@ def _check_conv_records(recs, label, dev):
             bf = r['bf']
             gate = None if r['gate'] is None else to(r['gate'].float())
             dw, dx = _spec(x, wh, nbr, r['n_out'], gy, bf, bf and (cout >= 16 or gate is not None), gate, x)
+            need_mag = r['need_dx'] and float(dx.norm()) > 0
+            amag = _spec(x.abs(), wh.abs(), nbr, r['n_out'], gy.abs(), bf, bf and (cout >= 16 or gate is not None),
+                         None if gate is None else gate.abs(), x)[1] if (need_mag or 'group' in r) else None
             dw_sum += dw
             tag = f'K={K} {cin}->{cout} rows {x.shape[0]}->{r["n_out"]}' + (' gated' if gate is not None else '') + \
                   (' bf16-rows' if r['x'].dtype == torch.bfloat16 else '') + ('' if bf else ' exact-f32') + \
                   (' gen-tap' if 'group' in r else '')
             kinds.add((K, cin, cout, gate is not None, r['x'].dtype == torch.bfloat16, bf, 'group' in r))
             if 'group' in r:                                     # 8 taps of a generative transposed conv: ONE data gradient
-                g = groups.setdefault(r['group'], dict(dx=torch.zeros_like(dx), n=0, tag=tag, before=r['before'], after=None,
-                                                      need=r['need_dx']))
+                g = groups.setdefault(r['group'], dict(dx=torch.zeros_like(dx), amag=torch.zeros_like(dx), n=0, tag=tag, before=r['before'],
+                                                      after=None, need=r['need_dx'], cout=cout))
                 g['dx'] += dx
+                g['amag'] += amag
                 g['n'] += 1
                 if 'after' in r:
                     g['after'] = r['after']
@@ -123,6 +155,7 @@ def _check_conv_records(recs, label, dev):
                 if e > worst_dx[0]:
                     worst_dx = (e, f'{tag} (tol applied {tol:.1e})')
                 assert e < tol, f'{label}: data gradient of {tag}: rel-L2 {e:.2e} (tol {tol:.1e})'
+                ratio_dx = max(ratio_dx, _dx_bound(after, want, amag, to(r['before']), K * cout, label, tag))
         if float(dw_sum.norm()) > 0:
             e = _rel(to(w.g), dw_sum)
             n_dw += 1
@@ -140,6 +173,7 @@ def _check_conv_records(recs, label, dev):
             if e > worst_dx[0]:
                 worst_dx = (e, f'{g["tag"]} x 8 (tol applied {tol:.1e})')
             assert e < tol, f'{label}: data gradient of the generative transposed conv {g["tag"]}: rel-L2 {e:.2e} (tol {tol:.1e})'
+            ratio_dx = max(ratio_dx, _dx_bound(after, want, g['amag'], to(g['before']), 8 * g['cout'], label, g['tag'] + ' x 8', n_acc=8))
     for ptr, rs in by_b.items():
         b = rs[0]['bias']
         bf_ = rs[0]['bias_from']
@@ -153,10 +187,14 @@ def _check_conv_records(recs, label, dev):
             n_db += 1
             if e > worst_db[0]:
                 worst_db = (e, f'{tuple(b.g.shape)} from column {bf_} ({len(rs)} launch(es), tol applied {tol:.1e})')
+            ratio_db = max(ratio_db, FS.check_bias_grad(f'{label}: {tuple(b.g.shape)}', to(b.g)[bf_:], want, mag,
+                                                        sum(r['n_out'] for r in rs)))
             assert e < tol, f'{label}: bias gradient {tuple(b.g.shape)}: rel-L2 {e:.2e} (tol {tol:.1e})'
     print(f'{label}: {len(recs)} convolution / Linear backwards, {len(kinds)} launch classes: {n_dw} weight gradients, worst rel-L2 '
           f'{worst_dw[0]:.2e} at {worst_dw[1]}; {n_dx} data gradients, worst {worst_dx[0]:.2e} at {worst_dx[1]}; {n_db} bias '
           f'gradients, worst {worst_db[0]:.2e} at {worst_db[1]} (tol {TOL:.0e} + eps-of-accumulated-buffer)')
+    print(f'{label}: per-element bounds (G = {FS.G:g}): worst data-gradient ratio |err| / (u sqrt(n) A) {ratio_dx:.3f}, worst bias-gradient '
+          f'ratio |err| / (u sqrt(rows) sum|gy|) {ratio_db:.3f}')
     return n_dw, n_dx, n_db, kinds
 
 
@@ -235,11 +273,14 @@ def _check_ops(ops, label, dev):
     return n
 
 
-def _recorded_step(det, make_batch, backward):
-    """one bf16 forward + backward of `det` with every backward launch recorded"""
+def _recorded_step(det, make_batch, backward, fwd=None):
+    """one bf16 forward + backward of `det` with every forward and backward launch recorded -> (conv backward records, other
+    backward records, forward records).  fwd: a callable that checks each forward record on the spot instead of keeping it (then
+    returned in place of the list)"""
     from embodiedscan_amd import engine as E
     E.PRECISION[0] = 'bf16'
     E.DEBUG_CONV, E.DEBUG_OPS = [], []
+    E.DEBUG_FWD = [] if fwd is None else fwd
     try:
         E.TAPE.clear()
         E.WEIGHT_VERSION[0] += 1
@@ -253,12 +294,24 @@ def _recorded_step(det, make_batch, backward):
         losses = det.forward(data['inputs'], data['data_samples'], mode='loss')
         backward()
         torch.cuda.synchronize()
-        recs, ops = E.DEBUG_CONV, E.DEBUG_OPS
+        recs, ops, frecs = E.DEBUG_CONV, E.DEBUG_OPS, E.DEBUG_FWD
     finally:
-        E.DEBUG_CONV = E.DEBUG_OPS = None
+        E.DEBUG_CONV = E.DEBUG_OPS = E.DEBUG_FWD = None
         E.PRECISION[0] = 'f32'
     assert all(np.isfinite(float(v)) for v in losses.values())
-    return recs, ops
+    return recs, ops, frecs
+
+
+def _check_fwd(frecs, label, dev, want=()):
+    """every forward record against its specification (tests/fwd_spec.py), the counts by entry point and the worst bound ratio per
+    launch class printed; want: entry points / kinds that must be among the records (the gate cannot go quiet when a dispatch rule
+    changes)"""
+    stats = FS.check_records(frecs, label, dev)
+    print(stats.report())
+    seen = set(stats.count) | {r['kind'] for r in frecs}
+    for w in want:
+        assert w in seen, f'{label}: no {w} forward launch was recorded (seen: {sorted(seen)})'
+    return stats
 
 
 def test_every_conv_backward_of_a_bf16_step_matches_its_specification():
@@ -270,7 +323,9 @@ def test_every_conv_backward_of_a_bf16_step_matches_its_specification():
     det = build_detector(os.path.join(ROOT, 'configs', 'mv_3ddet.py'), device=dev, seed=0).to(dev)
     scans = [make_scan(s, n_views=3, height=240, width=320, img_size=(192, 192), n_points=15000) for s in (21, 22)]
     dscans = [pipeline.upload_scan(s, dev) for s in scans]
-    recs, ops = _recorded_step(det, lambda: pipeline.make_batch(dscans), lambda: det._backward(None))
+    recs, ops, frecs = _recorded_step(det, lambda: pipeline.make_batch(dscans), lambda: det._backward(None))
+    _check_fwd(frecs, 'mv-3ddet', torch.device('cpu'), ('es_spconv_fwd_bf16_io', 'es_img_conv3_bf16', 'es_stem_pool_fwd',
+                                                       'es_gen_transpose_fwd_bf16', 'norm'))
     assert len(recs) > 80, len(recs)
     n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'mv-3ddet', torch.device('cpu'))
     assert n_dw > 60 and n_dx > 60 and n_db >= 1
@@ -285,7 +340,9 @@ def test_every_backward_launch_of_a_bf16_grounder_step_matches_its_specification
     dev = torch.device('cuda:0')
     cfg, det, sd = TG._small_grounder(dev)
     scans, anns, dscans = TG._grounding_batch(dev)
-    recs, ops = _recorded_step(det, lambda: pipeline.make_grounding_batch(dscans, anns), lambda: det._backward(None))
+    recs, ops, frecs = _recorded_step(det, lambda: pipeline.make_grounding_batch(dscans, anns), lambda: det._backward(None))
+    _check_fwd(frecs, 'mv-grounding (small)', torch.device('cpu'), ('attention', 'layernorm', 'contrastive'))
+    _assert_grounder_fwd({tuple(r['w'].shape) for r in frecs if r['kind'] == 'conv'}, sum(r['kind'] == 'attention' for r in frecs), 2, 128)
     n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'mv-grounding (small)', torch.device('cpu'))
     assert n_dw > 90 and n_dx > 90 and n_db > 10
     assert any(k[0] == 1 and k[1] == 256 and k[2] == 256 for k in kinds), 'no K = 1 256 -> 256 decoder launch was recorded'
@@ -300,7 +357,8 @@ def test_every_conv_backward_of_a_bf16_occupancy_step_matches_its_specification(
     dev = torch.device('cuda:0')
     cfg = TO._small_cfg()
     det, scan, occ, dscan = TO._occ_case(dev, cfg)
-    recs, ops = _recorded_step(det, lambda: pipeline.make_occ_batch([dscan], [occ]), lambda: E.TAPE.backward())
+    recs, ops, frecs = _recorded_step(det, lambda: pipeline.make_occ_batch([dscan], [occ]), lambda: E.TAPE.backward())
+    _check_fwd(frecs, 'occupancy (small)', torch.device('cpu'), ('es_dconv_fwd_bf16',))
     n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'occupancy (small)', torch.device('cpu'))
     assert n_dw > 80 and n_dx > 80
 
@@ -318,7 +376,10 @@ def test_config5_scale_occupancy_step_in_situ():
     sc = make_scan(4321, n_views=10, augment=False, render_device=str(dev))
     oc = make_occ_gt(sc, seed=0)
     dscan = pipeline.upload_scan(sc, dev)
-    recs, ops = _recorded_step(det, lambda: pipeline.make_occ_batch([dscan], [oc]), lambda: E.TAPE.backward())
+    chk = FS.Checker('occupancy (config-5 scale)', dev)
+    recs, ops, _ = _recorded_step(det, lambda: pipeline.make_occ_batch([dscan], [oc]), lambda: E.TAPE.backward(), fwd=chk)
+    print(chk.report())
+    assert 'es_dconv_fwd_bf16' in chk.stats.count
     n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'occupancy (config-5 scale)', dev)
     assert n_dw > 100 and n_dx > 90
     assert any(k[0] == 27 and k[1] == 3072 and k[2] == 3072 for k in kinds) and any(k[0] == 27 and k[1] == 768 for k in kinds)
@@ -349,9 +410,54 @@ def test_config4_scale_grounder_step_in_situ():
     scans = [make_scan(4100 + i, n_views=20, render_device='cuda:0') for i in range(2)]
     anns = [make_grounding_sample(s, seed=40 + i) for i, s in enumerate(scans)]
     dscans = [pipeline.upload_scan(s, dev) for s in scans]
-    recs, ops = _recorded_step(det, lambda: pipeline.make_grounding_batch(dscans, anns), lambda: det._backward(None))
+    chk = FS.Checker('mv-grounding (config-4 scale)', dev)
+    shapes, n_attn = set(), [0]
+
+    def fwd(rec):                                        # check on the spot, keep only what the coverage assertions need
+        if rec['kind'] == 'conv':
+            shapes.add(tuple(rec['w'].shape))
+        n_attn[0] += rec['kind'] == 'attention'
+        chk(rec)
+    recs, ops, _ = _recorded_step(det, lambda: pipeline.make_grounding_batch(dscans, anns), lambda: det._backward(None), fwd=fwd)
+    print(chk.report())
+    _assert_grounder_fwd(shapes, n_attn[0], 6, 2048)
+    assert all(k in chk.stats.count for k in ('es_attn_fwd', 'es_layernorm_fwd', 'es_contrastive_fwd'))
     n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'mv-grounding (config-4 scale)', dev)
     assert n_dw > 150 and n_dx > 150
     assert any(k[0] == 1 and k[1] == 256 and k[2] == 2048 for k in kinds)
     n = _check_ops(ops, 'mv-grounding (config-4 scale)', dev)
     assert n['attn'] == 6 * 3 and n['contrastive'] == 6
+
+
+def _assert_grounder_fwd(shapes, n_attn, n_layers, ffn):
+    """the decoder's forward launches: a K = 1 256 -> ffn Linear (the FFN), one attention per self / text / point attention of each
+    layer (shapes: the weight shapes of the recorded conv / Linear launches)"""
+    assert (1, 256, ffn) in shapes, f'no K = 1 256 -> {ffn} forward launch'
+    assert n_attn >= 3 * n_layers, n_attn
+
+
+def test_config2_scale_mv3ddet_step_in_situ():
+    """the SHIPPED mv-3ddet (configs/mv_3ddet.py) on 2 synthetic scans at the benchmark's scan shape (20 views of 480 x 640, 100 k
+    points): every forward launch of one bf16 step checked on the spot against its specification in f64 on the GPU (the halo K = 27
+    kernel's big-map dispatch, the image kernels and the fused stem at their real shapes), then every convolution backward."""
+    import time
+    from embodiedscan_amd import pipeline
+    from embodiedscan_amd.config import build_detector
+    from embodiedscan_amd.synth import make_scan
+    dev = torch.device('cuda:0')
+    det = build_detector(os.path.join(ROOT, 'configs', 'mv_3ddet.py'), device=dev, seed=0).to(dev)
+    scans = [make_scan(5100 + i, n_views=20, render_device='cuda:0') for i in range(2)]
+    dscans = [pipeline.upload_scan(s, dev) for s in scans]
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    t0 = time.time()
+    chk = FS.Checker('mv-3ddet (config-2 scale)', dev)
+    recs, ops, _ = _recorded_step(det, lambda: pipeline.make_batch(dscans), lambda: det._backward(None), fwd=chk)
+    print(chk.report())
+    for w in ('es_spconv_halo_bf16', 'es_img_conv3_bf16', 'es_stem_pool_fwd', 'es_gen_transpose_fwd_bf16', 'norm'):
+        assert w in chk.stats.count, f'no {w} forward launch at config-2 scale (seen: {sorted(chk.stats.count)})'
+    n_dw, n_dx, n_db, kinds = _check_conv_records(recs, 'mv-3ddet (config-2 scale)', dev)
+    torch.cuda.synchronize()
+    print(f'mv-3ddet (config-2 scale): peak device memory {torch.cuda.max_memory_allocated(dev) / 2 ** 30:.1f} GiB, '
+          f'wall time {time.time() - t0:.1f} s (recorded step + both checks)')
+    assert n_dw > 60 and n_dx > 60

@@ -114,3 +114,10 @@ def test_expansion_layers_stream_kernel_vs_row_gemm(case):
     ulp = (ys[65536].view(torch.int16).int() - ys[0].view(torch.int16).int()).abs()
     print(f'{case}: {mb:.0f} MB | row GEMM {ts[0]:.1f} us ({mb / ts[0]:.2f} TB/s) | stream kernel {ts[65536]:.1f} us ({mb / ts[65536]:.2f} TB/s) | differing bf16 values {int((ulp > 0).sum())}')
     assert int(ulp.max()) == 0
+    # independent reference: f64 on the bf16 operands, element by element (tests/fwd_spec.py), both kernels
+    import fwd_spec as FS
+    stats = FS.Stats(f'expansion {case}')
+    for on, name in ((65536, 'k_expand_bf16'), (0, 'k_rowgemm2_bf16')):
+        FS.check_conv(dict(kind='conv_affine', entry=name, x=x, w=w, nbr=None, n_out=n, round=True, scale=scale, shift=shift,
+                           res=res if with_res else None, act=1, y=ys[on]), dev, stats)
+    print(stats.report())

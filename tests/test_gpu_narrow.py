@@ -60,3 +60,19 @@ def test_conv1_kernels_vs_tiled_kernels(n_scans):
     print(f'{n_scans} scans: {n_in} -> {n_out} rows, {pairs:.1f} pairs/row: forward {out[0][2]:.1f} -> {out[1][2]:.1f} us (rel diff {ef:.1e}), '
           f'weight gradient {out[0][3]:.1f} -> {out[1][3]:.1f} us (rel diff {ew:.1e})')
     assert ef < 1e-5 and ew < 1e-4
+    # independent reference: f64 of the exact f32 operands, element by element (tests/fwd_spec.py), both kernel families
+    import math
+    import fwd_spec as FS
+    stats = FS.Stats(f'conv1 {n_scans} scans')
+    xd, dyd = x.double(), dy.double()
+    dw_want, dw_mag = torch.zeros(K, cin, cout, dtype=torch.float64, device=dev), torch.zeros(K, cin, cout, dtype=torch.float64, device=dev)
+    for k in range(K):
+        rows = torch.nonzero(nbr[:, k] >= 0).squeeze(1)
+        src = nbr[rows, k].long()
+        dw_want[k] = xd[src].t() @ dyd[rows]
+        dw_mag[k] = xd[src].abs().t() @ dyd[rows].abs()
+    for on, name in ((1, 'lane-per-channel'), (0, 'tiled')):
+        FS.check_conv(dict(kind='conv', entry=name, x=x, w=w, nbr=nbr, n_out=n_out, bias=bias, round=False, y=out[on][0]), dev, stats)
+        FS.bound_check(f'{name} weight gradient', out[on][1], dw_want, FS.U * math.sqrt(n_out) * dw_mag, torch.zeros_like(dw_want),
+                       False, f'wgrad {name}', stats)
+    print(stats.report())
