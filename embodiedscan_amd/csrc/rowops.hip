@@ -1159,7 +1159,12 @@ extern "C" int es_affine_act_fwd(const float* x, const float* scale, const float
   ES_CHECK_LAUNCH();
   return 0;
 }
-// dz = dy * relu'(y) ; dx (op)= dz * scale ; dres (op)= dz
+// dz = dy * act'(y) (ReLU: y > 0; ELU: y > 0 ? 1 : y + 1, the rule of k_norm_bwd_stats) ; dx (op)= dz * scale ; dres (op)= dz
+__device__ inline float act_bwd(float g, float y, int act) {
+  if (act == 1) return y > 0.f ? g : 0.f;
+  if (act == 2) return y > 0.f ? g : g * (y + 1.f);
+  return g;
+}
 __global__ void k_affine_act_bwd(const float* __restrict__ dy, const float* __restrict__ y,
                                  const float* __restrict__ scale, size_t n, int C, int act, float* __restrict__ dx,
                                  int acc_x, float* __restrict__ dres, int acc_r) {
@@ -1167,7 +1172,7 @@ __global__ void k_affine_act_bwd(const float* __restrict__ dy, const float* __re
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
     int c = (int)(e % C);
     float g = dy[e];
-    if (act && !(y[e] > 0.f)) g = 0.f;
+    if (act) g = act_bwd(g, y[e], act);
     if (dx) dx[e] = acc_x ? dx[e] + g * scale[c] : g * scale[c];
     if (dres) dres[e] = acc_r ? dres[e] + g : g;
   }
@@ -1180,10 +1185,8 @@ __global__ void k_affine_act_bwd4(const float4* __restrict__ dy, const float4* _
     float4 g = dy[e];
     if (act) {
       float4 v = y[e];
-      if (!(v.x > 0.f)) g.x = 0.f;
-      if (!(v.y > 0.f)) g.y = 0.f;
-      if (!(v.z > 0.f)) g.z = 0.f;
-      if (!(v.w > 0.f)) g.w = 0.f;
+      g.x = act_bwd(g.x, v.x, act); g.y = act_bwd(g.y, v.y, act);
+      g.z = act_bwd(g.z, v.z, act); g.w = act_bwd(g.w, v.w, act);
     }
     if (dx) {
       float4 s = scale[e % C4];
@@ -1198,7 +1201,8 @@ __global__ void k_affine_act_bwd4(const float4* __restrict__ dy, const float4* _
     }
   }
 }
-// the same with the activation y stored in bf16 (image backbone, round 3): only its sign is read
+// the same with the activation y stored in bf16 (image backbone, round 3): only its sign is read (ReLU only: the launcher refuses
+// act = 2, whose derivative y + 1 a bf16 y cannot give to f32 accuracy)
 __global__ void k_affine_act_bwd4_yh(const float4* __restrict__ dy, const uint2* __restrict__ y,
                                      const float4* __restrict__ scale, size_t n4, int C4, int act,
                                      float4* __restrict__ dx, int acc_x, float4* __restrict__ dres, int acc_r) {
@@ -1226,6 +1230,7 @@ __global__ void k_affine_act_bwd4_yh(const float4* __restrict__ dy, const uint2*
 }
 extern "C" int es_affine_act_bwd_yh(const float* dy, const void* y_bf16, const float* scale, size_t n, int C, int act,
                                     float* dx, int acc_x, float* dres, int acc_r, void* stream) {
+  if (act == 2) return -2;
   if (n == 0) return 0;
   if ((C % 4) || ((((uintptr_t)dy) | ((uintptr_t)scale) | ((uintptr_t)dx) | ((uintptr_t)dres)) & 15) || (((uintptr_t)y_bf16) & 7))
     return -7;

@@ -227,9 +227,12 @@ int es_bn_fold(const float* w, const float* b, const float* rm, const float* rv,
                float* shift, void* stream);
 int es_affine_act_fwd(const float* x, const float* scale, const float* shift, const float* res, size_t n, int C,
                       int act, float* y, void* stream);
+/* dz = dy * act'(y) on the stored output y (act 1 ReLU: y > 0; 2 ELU: y > 0 ? 1 : y + 1, as es_norm_bwd), dx (+)= dz * scale,
+ * dres (+)= dz; either output may be NULL */
 int es_affine_act_bwd(const float* dy, const float* y, const float* scale, size_t n, int C, int act, float* dx,
                       int acc_x, float* dres, int acc_r, void* stream);
-/* es_affine_act_bwd with the activation y stored in bf16 (only its sign is read); C % 4 == 0 */
+/* es_affine_act_bwd with the activation y stored in bf16 (only its sign is read); C % 4 == 0 and 16-byte aligned f32 operands
+ * (8-byte y_bf16), else -7.  act = 2 returns -2: y + 1 cannot be taken from a bf16 y to f32 accuracy.  Nothing is written on refusal. */
 int es_affine_act_bwd_yh(const float* dy, const void* y_bf16, const float* scale, size_t n, int C, int act, float* dx,
                          int acc_x, float* dres, int acc_r, void* stream);
 
