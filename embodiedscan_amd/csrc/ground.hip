@@ -362,6 +362,7 @@ __global__ __launch_bounds__(1024) void k_topk_sorted(const float* __restrict__ 
     unsigned long long kk = ~0ull;                      // padding sorts last
     if (i < n) {
       unsigned int u = __float_as_uint(vals[(size_t)b * L + i]);
+      if (u == 0x80000000u) u = 0u;                     // -0.0 == +0.0: the two zeros tie, and ties go to the lower row
       u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending order-preserving map
       kk = ((unsigned long long)(~u) << 32) | (unsigned int)i;    // descending value, ascending row
     }

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ Q, i
     for (int r = 0; r < 4; ++r) {
       float s0 = ok0 ? s[0][r] : -INFINITY, s1 = ok1 ? s[1][r] : -INFINITY;
       float mx = group16_max(fmaxf(s0, s1));
-      float mn = fmaxf(m[r], mx);                      // finite: every step has at least one valid key
+      float mn = fmaxf(m[r], mx);                      // finite: every step has at least one valid key (a sample WITHOUT a step: below)
       float corr = __expf(m[r] - mn);
       float p0 = __expf(s0 - mn), p1 = __expf(s1 - mn);
       l[r] = l[r] * corr + group16_sum(p0 + p1);
@@ -152,11 +152,15 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ Q, i
   for (int r = 0; r < 4; ++r) {
     int q = q0 + wv * 16 + kq * 4 + r;
     if (q >= Lq) continue;
-    float inv = 1.f / l[r];
+    // A sample without a valid key (klen[b] <= 0) never entered the loop: l = 0, o = 0, m = -inf.  It gets O = 0 and lse = -inf.
+    // Deliberate divergence: the reference's softmax over a fully masked row is NaN there (grounding section).  The
+    // backward kernels skip their key loops for such a sample as well (kvalid <= 0; lse is never read) and write exact zeros.
+    const bool any = l[r] > 0.f;
+    float inv = any ? 1.f / l[r] : 0.f;
     float* orow = O + ((size_t)b * Lq + q) * ldo + h * AT_D;
     orow[li] = o[0][r] * inv;
     orow[16 + li] = o[1][r] * inv;
-    if (li == 0) lse[((size_t)b * H + h) * Lq + q] = m[r] + __logf(l[r]);
+    if (li == 0) lse[((size_t)b * H + h) * Lq + q] = any ? m[r] + __logf(l[r]) : -INFINITY;
   }
 }
 
@@ -533,7 +537,7 @@ __global__ __launch_bounds__(256) void k_contrastive_fwd(const float* __restrict
                                                          float* __restrict__ rowmax) {
   extern __shared__ float ts[];                         // T * C
   const int b = blockIdx.y;
-  const int tl = min(tlen[b], T);
+  const int tl = min(min(tlen[b], T), Tout);            // tokens beyond the Tout written columns are not staged (nor in rowmax)
   for (int e = threadIdx.x; e < tl * C; e += 256) ts[e] = text[(size_t)b * T * C + e];
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -584,7 +588,7 @@ __global__ __launch_bounds__(256) void k_contrastive_bwd(const float* __restrict
                                                          float* __restrict__ ws, int safe) {
   extern __shared__ float sh[];                         // dv workgroups: the sample's text block [tl * C]
   const int b = blockIdx.y;
-  const int tl = min(tlen[b], T);
+  const int tl = min(min(tlen[b], T), Tout);            // a dlogits row holds Tout columns: the forward wrote no more
   const float inv = 1.f / sqrtf((float)C);
   const bool reduce = (dtext != nullptr) || (dbias != nullptr);
   if ((int)blockIdx.x < nA) {

@@ -352,9 +352,10 @@ def check_layernorm(rec, dev, stats):
 
 def check_attention(rec, dev, stats):
     """S = r(f32(q s)) r(k)^T (s = 1 / sqrt(32)), keys >= klen masked, lse = logsumexp(S), o = softmax(S) r(V).  The kernel runs the
-    online softmax: it rounds the UNNORMALISED probabilities exp(S - running max) to bf16 (relative error <= 2^-9 each, whatever the
+    online softmax: it rounds the UNNORMALISED probabilities exp(S - running max) to bf16 (relative error <= 2^-8 each: bf16 has 8 significant bits, whatever the
     running max), so o is held per element to (2^-8 + G u sqrt(Lk) + 2 dS) (P |r(V)|) with dS = G u sqrt(32) max_j (|r(qs)| |r(k)|^T)
-    the error of the score GEMM; lse to dS + G u sqrt(Lk) + 4 u |lse| + 1e-6 (the fast exponential)."""
+    the error of the score GEMM; lse to dS + G u sqrt(Lk) + 4 u |lse| + 1e-6 (the fast exponential).  A sample with klen <= 0 must
+    hold O = 0 and lse = -inf exactly."""
     B, H, Lq, Lk, bf = rec['B'], rec['H'], rec['Lq'], rec['Lk'], rec['bf']
     s = torch.tensor(0.17677669529663687, dtype=torch.float32)
     rr = _r if bf else _d
@@ -367,7 +368,9 @@ def check_attention(rec, dev, stats):
     dS = (G * U * math.sqrt(32) * (qs.abs() @ ks.abs().transpose(-1, -2)) * live).amax(-1)
     S = S.masked_fill(~live, -math.inf)
     lse = torch.logsumexp(S, -1)
-    P = torch.exp(S - lse[..., None])
+    # a sample without a valid key (klen <= 0): O = 0 and lse = -inf by definition (the reference's softmax is NaN there)
+    dead = (klen <= 0)[:, None, None].expand(B, H, Lq)
+    P = torch.where(dead[..., None], torch.zeros_like(S), torch.exp(S - lse.masked_fill(dead, 0.0)[..., None]))
     o = P @ vs
     mag = P @ vs.abs()
     label = f'{stats.label}: attention B={B} H={H} Lq={Lq} Lk={Lk}'
@@ -375,6 +378,10 @@ def check_attention(rec, dev, stats):
     got = rec['o'].to(dev).double().reshape(B, Lq, H, 32).permute(0, 2, 1, 3)
     bound_check(label + ' o', got, o, torch.zeros_like(o), rel_p[..., None] * mag / U, False, 'attention o', stats)
     lk = rec['lse'].to(dev).double().view(B, H, Lq)
+    if bool(dead.any()):
+        if not (bool(torch.isneginf(lk[dead]).all()) and bool((got[dead] == 0).all())):
+            raise AssertionError(f'{label}: a sample without a valid key must get O = 0 and lse = -inf')
+        lk, lse = lk.masked_fill(dead, 0.0), lse.masked_fill(dead, 0.0)
     lb = dS + G * U * math.sqrt(Lk) + 4 * U * lse.abs() + 1e-6
     bound_check(label + ' lse', lk, lse, torch.zeros_like(lse), lb / U, False, 'attention lse', stats)
 

@@ -582,3 +582,25 @@ def test_host_thread_pool_is_capped_by_the_granted_cores(monkeypatch):
         monkeypatch.undo()
         assert torch.get_num_threads() == have
         E._HOST_SETTLED[0] = False
+
+
+def test_lsa_port_matches_scipy_on_heavily_tied_integer_costs():
+    """tests/ground_spec.py lsa_port / lsa_port_np (the specification es_ground_match's assignment is held to) against the installed
+    scipy.optimize.linear_sum_assignment: 400 random integer-valued matrices with few distinct values (every augmenting step meets
+    ties), nr <= nc, nr = 0 and nr = nc among them -- identical column for every row, not just an equal total"""
+    import numpy as np
+    from scipy.optimize import linear_sum_assignment
+    import ground_spec as S
+    rng = np.random.default_rng(17)
+    seen = set()
+    for it in range(400):
+        nc = int(rng.integers(1, 14)) if it % 10 else int(rng.integers(20, 41))
+        nr = (0, nc, int(rng.integers(0, nc + 1)))[min(it % 7, 2)]
+        cost = rng.integers(0, int(rng.choice([2, 3, 5])), (nr, nc)).astype(np.float64)
+        if it % 5 == 0:
+            cost[:, rng.integers(0, nc, max(nc // 3, 1))] = 100.0           # whole columns at the nan_to_num value
+        seen.add((nr == 0, nr == nc))
+        ri, ci = linear_sum_assignment(cost)
+        a, b = S.lsa_port(cost), S.lsa_port_np(cost)
+        assert list(ri) == list(range(nr)) and a == [int(c) for c in ci] and b == a, (it, cost.tolist(), a, b, ci.tolist())
+    assert {(True, False), (False, True), (False, False)} <= seen
