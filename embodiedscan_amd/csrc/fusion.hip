@@ -247,3 +247,163 @@ extern "C" int es_point_sample_bwd(const int* coords, int n, int V, const float*
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- Prefix fusion (continuous occupancy, embodiedscan/models/detectors/embodied_occ.py:165-203) --------------------------
+// The reference builds the image volume of prefix t by calling batch_point_sample on views 0..t, for every t: V (V + 1) / 2
+// view gathers per voxel.  Here ONE pass over the views keeps the running sum and writes the mean of every prefix as it goes:
+// row t * n + i of `out` is what k_point_sample_fwd<true> writes to row i when called with t + 1 views -- the same f32 terms
+// added in the same ascending order, the same division -- so the result is bit-identical to the V separate calls.
+// Same shape as k_point_sample_fwd: one wave per voxel, 16 voxels per workgroup, the meta block staged once in LDS, lane v
+// projects view v, lanes over channels for the fetch and for the store.  Only the running sum lives in registers (8 per
+// lane at C = 512); each prefix row goes out as soon as its view is added, coalesced along C.  V <= 64 (one ballot).
+__global__ __launch_bounds__(256) void k_point_sample_prefix_fwd(const int* __restrict__ coords, const float* __restrict__ pts,
+                                                                 int n, const float* __restrict__ meta, int meta_stride, int V,
+                                                                 const float* __restrict__ feats, int Hf, int Wf, int C,
+                                                                 float* __restrict__ out, int ldo, int* __restrict__ pix,
+                                                                 int* __restrict__ cnt) {
+  __shared__ float metaS[PS_MAXMETA];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * PS_PTS, i1 = min(n, i0 + PS_PTS);
+  const int b0 = coords[(size_t)i0 * 4], b1 = coords[(size_t)(i1 - 1) * 4];
+  const int nmeta = ES_FUSE_PROJ + 16 * V;
+  const bool staged = (b0 == b1) && (nmeta <= PS_MAXMETA);   // workgroup-uniform
+  if (staged)
+    for (int e = threadIdx.x; e < nmeta; e += 256) metaS[e] = meta[(size_t)b0 * meta_stride + e];
+  __syncthreads();
+  const int MAXC = 8;                                   // supports C <= 512
+  for (int i = i0 + wv; i < i1; i += 4) {               // wave-uniform
+    int4 c = ((const int4*)coords)[i];
+    const float* m = staged ? metaS : meta + (size_t)c.x * meta_stride;
+    float x = pts[(size_t)i * 3], y = pts[(size_t)i * 3 + 1], z = pts[(size_t)i * 3 + 2];
+    undo_aug(m, x, y, z);
+    bool valid = false;
+    int p = -1;
+    if (lane < V) {
+      p = project_view(m, m + ES_FUSE_PROJ + lane * 16, x, y, z, Hf, Wf, valid);
+      pix[(size_t)i * V + lane] = p;
+    }
+    const unsigned long long vm = __ballot(valid);
+    if (lane < V) cnt[(size_t)lane * n + i] = (int)__popcll(vm & ((2ull << lane) - 1ull));   // valid views among 0..lane
+    float acc[MAXC];
+#pragma unroll
+    for (int q = 0; q < MAXC; ++q) acc[q] = 0.f;
+    for (int u = 0; u < V; ++u) {                        // views in ascending order: the summation order of the V separate calls
+      const int pu = __shfl(p, u, 64);
+      if (pu >= 0) {
+        const size_t off = (((size_t)c.x * V + u) * Hf * Wf + pu) * C;
+#pragma unroll
+        for (int q = 0; q < MAXC; ++q) {
+          int ch = lane + q * 64;                        // sum over ALL views, not masked
+          if (ch < C) acc[q] += feats[off + ch];
+        }
+      }
+      const int nvalid = (int)__popcll(vm & ((2ull << u) - 1ull));
+      const float d = (float)max(nvalid, 1);
+      float* row = out + ((size_t)u * n + i) * ldo;
+#pragma unroll
+      for (int q = 0; q < MAXC; ++q) {
+        int ch = lane + q * 64;
+        if (ch < C) row[ch] = nvalid > 0 ? __fdiv_rn(acc[q], d) : 0.f;
+      }
+    }
+  }
+}
+extern "C" int es_point_sample_prefix_fwd_pts(const int* coords, const float* points, int n, const float* meta, int meta_stride,
+                                              int V, const float* feats, int Hf, int Wf, int C, float* out, int ldo, int* pix,
+                                              int* cnt, void* stream) {
+  if (n <= 0 || V <= 0) return 0;
+  if (C > 512) return -4;
+  if (V > 64) return -9;
+  hipLaunchKernelGGL(k_point_sample_prefix_fwd, dim3(es_cdiv(n, PS_PTS)), dim3(256), 0, (hipStream_t)stream, coords, points, n,
+                     meta, meta_stride, V, feats, Hf, Wf, C, out, ldo, pix, cnt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// Backward of the prefix fusion.  View v of voxel i feeds every prefix t >= v, so the gradient that hit (i, v) carries to its
+// feature-map pixel is the SUFFIX sum g(i, v) = sum_{t = V-1 .. v, cnt[t][i] > 0} dout[t n + i] / cnt[t][i], taken from t = V - 1
+// downward.  The hit lists are those of es_point_sample_bwd (k_ps_link on the LAST prefix's counts: cnt[t][i] never falls with t,
+// so a voxel without a valid view in prefix V - 1 has none in any); the gather walks the frames of each hit in registers and adds
+// the finished g(i, v) in ascending voxel order.  No float atomics, every pixel written, bit-reproducible.
+__global__ __launch_bounds__(256) void k_ps_prefix_gather(const int* __restrict__ head, const int* __restrict__ next, int n_pix,
+                                                          int n, int V, int HW, const float* __restrict__ dout, int ldo,
+                                                          const int* __restrict__ cnt, int C, float* __restrict__ dfeats,
+                                                          int accumulate) {
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (g >= n_pix) return;
+  const int v = (g / HW) % V;                             // the view this pixel belongs to: images are (sample, view)-major
+  float acc[PS_MAXC];
+#pragma unroll
+  for (int q = 0; q < PS_MAXC; ++q) acc[q] = 0.f;
+  const int h0 = head[g];
+  if (h0 >= 0) {
+    int last = -1;
+    while (true) {
+      int mine = 0x7fffffff, got = 0;                     // got is wave-uniform
+      for (int h = h0; h >= 0; h = next[h]) {             // wave-uniform walk
+        if (h <= last) continue;
+        if (got < 64) {
+          if (lane == got) mine = h;
+          ++got;
+        } else {                                          // keep the 64 smallest: replace the current maximum
+          int mx = es_wave_max_i(mine);
+          if (h < mx && mine == mx) mine = h;
+        }
+      }
+      if (got == 0) break;
+      for (int r = 0; r < got; ++r) {
+        const int m = es_wave_min_i(mine);
+        const int i = m / V;
+        float gs[PS_MAXC];
+#pragma unroll
+        for (int q = 0; q < PS_MAXC; ++q) gs[q] = 0.f;
+        for (int t = V - 1; t >= v; --t) {                // suffix sum over the prefixes this view is part of
+          const int ct = cnt[(size_t)t * n + i];
+          if (ct <= 0) continue;
+          const float inv = __fdiv_rn(1.f, (float)ct);
+          const float* row = dout + ((size_t)t * n + i) * ldo;
+#pragma unroll
+          for (int q = 0; q < PS_MAXC; ++q) {
+            int ch = lane + q * 64;
+            if (ch < C) gs[q] = fmaf(row[ch], inv, gs[q]);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < PS_MAXC; ++q) acc[q] += gs[q];
+        if (mine == m) mine = 0x7fffffff;
+        last = m;
+      }
+      if (got < 64) break;                                // the walk has seen every remaining hit
+    }
+  }
+  float* f = dfeats + (size_t)g * C;
+#pragma unroll
+  for (int q = 0; q < PS_MAXC; ++q) {
+    int ch = lane + q * 64;
+    if (ch < C) f[ch] = accumulate ? (f[ch] + acc[q]) : acc[q];
+  }
+}
+extern "C" int es_point_sample_prefix_bwd(const int* coords, int n, int V, const float* dout, int ldo, const int* pix,
+                                          const int* cnt, int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next,
+                                          int accumulate, void* stream) {
+  if (C > 64 * PS_MAXC) return -4;
+  const long long n_pix = (long long)n_img * Hf * Wf;
+  if (n_pix <= 0 || V <= 0) return 0;
+  if (n_pix >= (1ll << 31) || (long long)n * V >= (1ll << 31)) return -6;
+  hipStream_t st = (hipStream_t)stream;
+  ES_TRY(hipMemsetAsync(head, 0xff, (size_t)n_pix * sizeof(int), st));
+  if (n > 0) {
+    int g = es_cdiv((long long)n * V, 256);
+    hipLaunchKernelGGL(k_ps_link, dim3(g > 8192 ? 8192 : g), dim3(256), 0, st, coords, n, V, pix, cnt + (size_t)(V - 1) * n, Hf * Wf,
+                       head, next);
+    ES_CHECK_LAUNCH();
+  }
+  if (V == 1)                                             // one prefix of one view IS es_point_sample_bwd: the same kernel, the same bits
+    hipLaunchKernelGGL(k_ps_gather, dim3(es_cdiv(n_pix, 4)), dim3(256), 0, st, head, next, (int)n_pix, V, dout, ldo, cnt, C, dfeats,
+                       accumulate);
+  else
+    hipLaunchKernelGGL(k_ps_prefix_gather, dim3(es_cdiv(n_pix, 4)), dim3(256), 0, st, head, next, (int)n_pix, n, V, Hf * Wf, dout, ldo,
+                       cnt, C, dfeats, accumulate);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

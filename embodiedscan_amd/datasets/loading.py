@@ -264,7 +264,7 @@ class ScanPipeline:
     def __init__(self, n_images=20, ordered=False, n_points=100000, view_points=None, img_scale=(480, 480),
                  flip=False, flip_h=0.5, flip_v=0.5, rst=False, rot_range=(-0.087266, 0.087266), scale_range=(.9, 1.1),
                  trans_std=(.1, .1, .1), with_occupancy=False, view_masks=False, point_range=None, exact_draws=True,
-                 device_draws=False):
+                 device_draws=False, sweeps=False):
         # exact_draws: PointSample replays the reference's RandomState stream pick for pick (parity tests, golden vectors);
         # False: same distribution from O(k) draws (draw_without_order) -- 1.7 x the scans per core
         self.exact_draws = bool(exact_draws)
@@ -284,6 +284,10 @@ class ScanPipeline:
         # host never sees 3-D coordinates) and the device drops the out-of-range ones when it voxelises -- the cloud is
         # thinner by the out-of-range fraction.  Kept in the scan so the consumer can apply it.
         self.point_range = None if point_range is None else tuple(point_range)
+        # continuous perception (cont-* configs: AggregateMultiViewPoints(save_slices=True) ... ConstructMultiSweeps): the scan keeps
+        # ALL V * view_points points in frame order, no aggregated draw is made (and no RNG value consumed for one), and it
+        # carries `points_slice_indices` + the per-prefix `gt_occupancy_masks`
+        self.sweeps = bool(sweeps)
 
     @classmethod
     def from_cfg(cls, pipeline):
@@ -321,10 +325,20 @@ class ScanPipeline:
                 kw['point_range'] = tuple(t['point_cloud_range'])
             elif ty == 'ConstructMultiViewMasks':
                 kw['view_masks'] = True
-            elif ty in ('AggregateMultiViewPoints', 'Pack3DDetInputs'):
+            elif ty == 'AggregateMultiViewPoints':
+                kw['_slices'] = bool(t.get('save_slices', False))
+            elif ty == 'ConstructMultiSweeps':
+                kw['sweeps'] = True
+            elif ty == 'Pack3DDetInputs':
                 pass
             else:
                 raise NotImplementedError(f'pipeline transform {ty}')
+        slices = kw.pop('_slices', False)
+        if kw.get('sweeps'):
+            assert slices, 'ConstructMultiSweeps needs AggregateMultiViewPoints(save_slices=True) (multiview.py:181)'
+            # a top-level PointSample would re-draw the aggregated cloud after the slice indices were saved: the slices would
+            # then cut a shuffled cloud and mean nothing (the reference's cont-* configs comment that transform out)
+            assert 'n_points' not in kw, 'ConstructMultiSweeps cannot be combined with a top-level PointSample'
         return cls(**kw)
 
     def __call__(self, info, rng, alloc=None):
@@ -365,7 +379,7 @@ class ScanPipeline:
         if self.device_draws:
             # the device draws cover the `replace=False` law only: enough valid pixels in every frame, enough aggregated points,
             # no PointsRangeFilter between the draws -- else the host draws (O(k)) take over for this scan
-            on_device = (self.point_range is None and len(depths) * self.view_points >= self.n_points and
+            on_device = (not self.sweeps and self.point_range is None and len(depths) * self.view_points >= self.n_points and
                          len(depths) <= 256 and all(int(np.count_nonzero(d != 0)) >= self.view_points for d in depths))   # (14 x faster than count_nonzero(d) on f32)
             if not on_device:
                 for j, d in enumerate(depths):
@@ -386,12 +400,19 @@ class ScanPipeline:
         # PointsRangeFilter sits BETWEEN the aggregation and PointSample(n_points) in the occupancy pipeline
         # (configs/occupancy/mv-occ_...py:121-123, transforms/points.py:246-263): drop the aggregated points outside the
         # range (unless fewer than 100 survive), THEN draw -- so the draw's population is the filtered cloud
+        slice_indices = None
+        if self.sweeps:
+            # AggregateMultiViewPoints(save_slices=True) (multiview.py:143-156,166-167): the cumulative per-frame point counts of the
+            # UNFILTERED cloud.  PointsRangeFilter runs after they were saved and does not update them (points.py:256-263), so
+            # ConstructMultiSweeps (multiview.py:183-216) cuts prefix t as the first slice[t + 1] rows of the FILTERED cloud: rows of
+            # later frames slide into earlier prefixes by the number of points the filter removed.  Kept as is.
+            slice_indices = [0] + np.cumsum(np.bincount(sel_view, minlength=len(depths))).tolist()
         if self.point_range is not None and not on_device and len(sel_pix):
             keep = points_in_range(depths, depth_intr, extr, sel_view, sel_pix, self.point_range)
             if int(keep.sum()) >= 100:
                 sel_view, sel_pix = sel_view[keep], sel_pix[keep]
         # PointSample(n_points) over the aggregated cloud (points.py:189-206)
-        if not on_device and len(sel_pix):
+        if not on_device and len(sel_pix) and not self.sweeps:
             pick = draw_without_order(rng, len(sel_pix), self.n_points, self.exact_draws and not self.device_draws)
             sel_view, sel_pix = sel_view[pick], sel_pix[pick]
         aug, aug_meta = draw_augmentation(self.aug, rng)
@@ -430,6 +451,16 @@ class ScanPipeline:
                     for j in range(1, len(vm) - 1):
                         m = np.logical_or(m, vm[j])
                     scan['gt_occupancy_masks'] = m
+                if self.sweeps:
+                    # ConstructMultiSweeps (multiview.py:205-227): prefix t sees the OR of the visibility masks of frames 0 .. t
+                    # (every frame contributes here, unlike ConstructMultiViewMasks above)
+                    m, ms = vm[0], [vm[0]]
+                    for j in range(1, len(vm)):
+                        m = np.logical_or(m, vm[j])
+                        ms.append(m)
+                    scan['gt_occupancy_masks'] = ms
+        if slice_indices is not None:
+            scan['points_slice_indices'] = slice_indices
         if self.point_range is not None:
             scan['point_range'] = self.point_range
         if 'visible_instance_masks' in ann:

@@ -12,8 +12,10 @@ class Det3DDataPreprocessor:
     RING = 2                                     # persistent output buffers per image geometry (see forward())
 
     def __init__(self, mean=None, std=None, bgr_to_rgb=False, rgb_to_bgr=False, pad_size_divisor=1, pad_value=0,
-                 voxel=False, device=None, **kw):
+                 voxel=False, batchwise_inputs=False, device=None, **kw):
         assert not voxel, 'voxel=True (mmcv hard/dynamic voxelisation) is not used by the shipped configs'
+        # continuous perception (cont-* configs): ONE incoming sample becomes one data sample per prefix (batchwise_samples)
+        self.batchwise_inputs = bool(batchwise_inputs)
         self.mean, self.std = list(mean or [0, 0, 0]), list(std or [1, 1, 1])
         self.flip = bool(bgr_to_rgb or rgb_to_bgr)
         self.pad_size_divisor, self.pad_value = pad_size_divisor, pad_value
@@ -34,8 +36,38 @@ class Det3DDataPreprocessor:
                 return t.device
         return torch.device('cuda', torch.cuda.current_device())
 
+    @staticmethod
+    def batchwise_samples(samples):
+        """data_preprocessor.py:176-207 of the reference: the one sample of a continuous batch -> T samples, one per prefix.  The
+        copies share meta and gt_occupancy; copy t carries entry t of the list-valued gt_occupancy_masks and, where the sample
+        has per-prefix boxes (labels_3d a list), entry t of those.  T is the length of whichever list is present (the reference
+        takes len(labels_3d), which its ConstructMultiSweeps makes as long as the mask list)."""
+        from ...structures import Det3DDataSample, InstanceData
+        src = samples[0]
+        gi = src.gt_instances_3d
+        labels = getattr(gi, 'labels_3d', None)
+        per_prefix_boxes = isinstance(labels, (list, tuple))
+        masks = getattr(src, 'gt_occupancy_masks', None)
+        assert per_prefix_boxes or isinstance(masks, (list, tuple)), \
+            'batchwise_inputs: the sample carries neither per-prefix gt_occupancy_masks nor per-prefix labels_3d'
+        T = len(labels) if per_prefix_boxes else len(masks)
+        out = []
+        for t in range(T):
+            ds = Det3DDataSample(src.metainfo, gi)
+            for k, v in src.__dict__.items():
+                if k not in ('metainfo', 'gt_instances_3d'):
+                    setattr(ds, k, v)
+            if per_prefix_boxes:
+                ds.gt_instances_3d = InstanceData(bboxes_3d=gi.bboxes_3d[t], labels_3d=labels[t])
+            if isinstance(masks, (list, tuple)):
+                ds.gt_occupancy_masks = masks[t]
+            out.append(ds)
+        return out
+
     def forward(self, data, training=False):
         inputs, samples = data['inputs'], data.get('data_samples')
+        if self.batchwise_inputs and samples is not None:
+            samples = self.batchwise_samples(samples)
         out = {}
         dev = self._target_device(inputs)
         if 'points' in inputs:

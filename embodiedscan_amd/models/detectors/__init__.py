@@ -1,0 +1,1 @@
+from .embodied_occ import EmbodiedOccPredictor  # noqa: F401

@@ -86,7 +86,7 @@ def _host_tensors(scan):
 def _finish(d, scan):
     d.update(meta=scan['meta'], gt_boxes=torch.as_tensor(scan['gt_boxes']), gt_labels=torch.as_tensor(scan['gt_labels']))
     for k in ('gt_occupancy', 'gt_occupancy_masks', 'visible_occupancy_masks', 'visible_instance_masks', 'point_range',
-              'text', 'tokens_positive', 'draw'):
+              'text', 'tokens_positive', 'draw', 'points_slice_indices'):
         if k in scan:
             d[k] = scan[k]
     return d
@@ -260,6 +260,32 @@ def make_occ_batch(dscans, occ_gts=None):
         ds.gt_occupancy = torch.as_tensor(occ['gt_occupancy'])
         m = occ.get('gt_occupancy_masks')
         ds.gt_occupancy_masks = None if m is None else torch.as_tensor(m)
+    return data
+
+
+def prefix_lengths(points_slice_indices, n_rows):
+    """rows of the cloud that prefix t = 0 .. T-1 holds.  ConstructMultiSweeps (multiview.py:183-216) concatenates the slices
+    [s[0]:s[1]], [s[1]:s[2]], ... of the cloud it is handed; the indices were saved BEFORE PointsRangeFilter thinned that cloud
+    (multiview.py:154-167, points.py:256-263) and are not updated, so prefix t is the first min(s[t + 1], n_rows) rows of the
+    filtered cloud -- kept as the reference does it"""
+    return [min(int(e), int(n_rows)) for e in points_slice_indices[1:]]
+
+
+def make_cont_occ_batch(dscan, occ=None):
+    """`data` dict for EmbodiedOccPredictor.train_step from ONE scan of a sweeps pipeline (ScanPipeline(sweeps=True)): `points`
+    is the list of the T cumulative clouds ConstructMultiSweeps builds (multiview.py:183-216) -- here T row-prefix VIEWS of the one
+    un-projected device buffer (prefix t = its first points_slice_indices[t + 1] rows; no copy) -- and the single data sample
+    carries `gt_occupancy` and the list-valued per-prefix `gt_occupancy_masks`; Det3DDataPreprocessor(batchwise_inputs=True)
+    turns it into T samples.  occ None: the scan carries both itself."""
+    sl = dscan['points_slice_indices']
+    data = make_batch([dscan])
+    pts = data['inputs']['points'][0]
+    data['inputs']['points'] = [pts[:e] for e in prefix_lengths(sl, pts.shape[0])]
+    occ = occ if occ is not None else dscan
+    ds = data['data_samples'][0]
+    ds.gt_occupancy = torch.as_tensor(occ['gt_occupancy'])
+    ds.gt_occupancy_masks = [torch.as_tensor(m) for m in occ['gt_occupancy_masks']]
+    assert len(ds.gt_occupancy_masks) == len(sl) - 1, 'one visibility mask per prefix'
     return data
 
 

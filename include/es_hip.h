@@ -269,6 +269,19 @@ int es_point_sample_fwd_pts(const int* coords, const float* points, int n, const
  * caller needs no memset).  n_img = samples * V; head: n_img*Hf*Wf ints, next: n*V ints of scratch. */
 int es_point_sample_bwd(const int* coords, int n, int V, const float* dout, int ldo, const int* pix, const int* cnt,
                         int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next, int accumulate, void* stream);
+/* prefix fusion of the continuous occupancy detector (embodied_occ.py:165-203): ONE pass over the V views writes the image
+ * volume of every prefix 0..t.  out row t*n + i, columns [0, C) = what es_point_sample_fwd_pts writes to row i when called with
+ * t + 1 views, bit for bit (frame-major rows: the batch-major order of the dense neck with B = V); pix (n,V) as the sibling;
+ * cnt (V,n): cnt[t*n + i] = valid views among 0..t.  -4: C > 512; -9: V > 64. */
+int es_point_sample_prefix_fwd_pts(const int* coords, const float* points, int n, const float* meta, int meta_stride, int V,
+                                   const float* feats, int Hf, int Wf, int C, float* out, int ldo, int* pix, int* cnt,
+                                   void* stream);
+/* its backward: dfeats pixel (v, p) (+)= sum over the voxels i that hit it, in ascending i, of
+ * g(i, v) = sum_{t = V-1 .. v, cnt[t*n + i] > 0} dout[t*n + i] / cnt[t*n + i] (added from t = V - 1 downward).  Deterministic gather,
+ * every pixel written; dout (V*n, ldo), scratch as es_point_sample_bwd. */
+int es_point_sample_prefix_bwd(const int* coords, int n, int V, const float* dout, int ldo, const int* pix, const int* cnt,
+                               int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next, int accumulate,
+                               void* stream);
 
 /* ---- A12 target assignment.  fcaf3d_head.py:1578-1664 --------------------------------------------- */
 /* level_off: HOST array n_levels+1.  rot_neg: (G,9) row-major R(-euler) (ZXY) computed on the host.
