@@ -6,8 +6,11 @@
 //     reference's 81-iteration Python loop.  Every class statistic the three losses need is linear in the softmax
 //     probabilities:  A_c = sum_mask p_c,  B_c = sum_mask p_c [t == c],  N_c = #(t == c),  n = #mask, so one pass
 //     accumulates them (f64), a one-block kernel turns them into the loss values and into the coefficients
-//     dL/dA_c, dL/dB_c, and a second pass writes dL/dlogits = softmax-backward of (alpha_c + beta_c [t == c]) plus the
-//     cross-entropy term.
+//     alpha_c = dL/dA_c (what p_c of a voxel of ANOTHER class sees) and gamma_c = dL/dA_c + dL/dB_c (what p_c of a voxel of
+//     class c sees), and a second pass writes dL/dlogits = softmax-backward of (t == c ? gamma_c : alpha_c) plus the
+//     cross-entropy term.  gamma_c is formed analytically: dL/dA_c and dL/dB_c hold equal and opposite terms (-g/rest against
+//     +g/rest, -gR/R against +gR/R, gP (inter - D)/D^2 against gP/D) that grow without bound as a precision or a recall goes to
+//     zero, and their f32 sum then loses everything else.
 #include "common.h"
 #include "../../include/es_hip.h"
 
@@ -125,13 +128,13 @@ __device__ inline double bce1(double x) { return -fmax(log(x), -100.0); }
 __device__ inline double bce1_grad(double x) { return (x - 1.0) / fmax((1.0 - x) * x, 1e-12); }
 
 // one block: losses (out[0] CE, out[1] sem_scal, out[2] geo_scal, out[3] their weighted sum) and coeff[c] = alpha_c,
-// coeff[C + c] = beta_c (already multiplied by `weight`), coeff[2C] = weight / n_mask (cross-entropy scale)
+// coeff[C + c] = gamma_c (already multiplied by `weight`), coeff[2C] = weight / n_mask (cross-entropy scale)
 __global__ void k_occ_coeffs(const double* __restrict__ stats, int C, float weight, float* __restrict__ coeff,
                              float* __restrict__ out, float* __restrict__ total_acc) {
   __shared__ double s_loss[256], s_cnt[256];
   const int c = threadIdx.x;
   const double n = stats[3 * C];
-  double alpha = 0.0, beta = 0.0, lc = 0.0, counted = 0.0;
+  double alpha = 0.0, gamma = 0.0, lc = 0.0, counted = 0.0;
   if (c < C) {
     double A = stats[c], B = stats[C + c], N = stats[2 * C + c];
     if (N > 0.0) {                                           // occ_loss.py:113: classes present in the target only
@@ -140,19 +143,18 @@ __global__ void k_occ_coeffs(const double* __restrict__ stats, int C, float weig
         double pr = B / A;
         lc += bce1(pr);
         double g = bce1_grad(pr);
-        beta += g / A;
         alpha += -g * B / (A * A);
+        gamma += g * (A - B) / (A * A);                        // -g B / A^2 + g / A
       }
       double rc = B / N;
       lc += bce1(rc);
-      beta += bce1_grad(rc) / N;
+      gamma += bce1_grad(rc) / N;
       double rest = n - N;
       if (rest > 0.0) {
         double sp = (rest - (A - B)) / rest;
         lc += bce1(sp);
         double g = bce1_grad(sp);
-        alpha += -g / rest;
-        beta += g / rest;
+        alpha += -g / rest;                                    // (+g / rest on the target class: gamma keeps neither)
       }
     }
   }
@@ -166,7 +168,7 @@ __global__ void k_occ_coeffs(const double* __restrict__ stats, int C, float weig
   const double count = s_cnt[0];
   const double sem = count > 0.0 ? s_loss[0] / count : 0.0;
   if (c < C) {
-    double a = count > 0.0 ? alpha / count : 0.0, b = count > 0.0 ? beta / count : 0.0;
+    double a = count > 0.0 ? alpha / count : 0.0, gm = count > 0.0 ? gamma / count : 0.0;
     if (c == 0) {                                            // geo_scal_loss: empty (class 0) vs non-empty, eps 1e-6
       const double eps = 1e-6;
       double A0 = stats[0], B0 = stats[C], N0 = stats[2 * C];
@@ -175,7 +177,7 @@ __global__ void k_occ_coeffs(const double* __restrict__ stats, int C, float weig
       double P = inter / D, Rc = inter / R, Sp = B0 / S;
       double gP = bce1_grad(P), gR = bce1_grad(Rc), gS = bce1_grad(Sp);
       a += gP * (inter - D) / (D * D) - gR / R;
-      b += gP / D + gR / R + gS / S;
+      gm += gP * inter / (D * D) + gS / S;                     // the gR / R pair drops out; gP ((inter - D) / D^2 + 1 / D)
       double geo = bce1(P) + bce1(Rc) + bce1(Sp);
       double ce = stats[3 * C + 1] / n;                      // n == 0 -> NaN, like CrossEntropyLoss(reduction='mean')
       out[0] = (float)ce;
@@ -187,7 +189,7 @@ __global__ void k_occ_coeffs(const double* __restrict__ stats, int C, float weig
       coeff[2 * C] = (float)((double)weight / n);
     }
     coeff[c] = (float)(a * (double)weight);
-    coeff[C + c] = (float)(b * (double)weight);
+    coeff[C + c] = (float)(gm * (double)weight);
   }
 }
 
@@ -195,12 +197,12 @@ __global__ __launch_bounds__(256) void k_occ_grad(const float* __restrict__ logi
                                                   int C, const float* __restrict__ coeff, float* __restrict__ dlogits, int ldg) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwave = gridDim.x * 4;
-  float al[OCC_PER], be[OCC_PER];
+  float al[OCC_PER], ga[OCC_PER];
 #pragma unroll
   for (int q = 0; q < OCC_PER; ++q) {
     int c = lane + q * 64;
     al[q] = c < C ? coeff[c] : 0.f;
-    be[q] = c < C ? coeff[C + c] : 0.f;
+    ga[q] = c < C ? coeff[C + c] : 0.f;
   }
   const float ce_scale = coeff[2 * C];
   for (int i = wave; i < n; i += nwave) {
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void k_occ_grad(const float* __restrict__ logi
 #pragma unroll
     for (int q = 0; q < OCC_PER; ++q) {
       int c = lane + q * 64;
-      g[q] = al[q] + (c == t ? be[q] : 0.f);
+      g[q] = c == t ? ga[q] : al[q];
       dot += p[q] * g[q];
     }
     dot = es_wave_sum(dot);
