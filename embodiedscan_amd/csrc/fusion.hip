@@ -248,6 +248,131 @@ extern "C" int es_point_sample_bwd(const int* coords, int n, int V, const float*
   return 0;
 }
 
+// ---- View-window fusion (continuous detection, embodiedscan/models/detectors/embodied_det3d.py:90-207) ---------------------------
+// The reference runs the 2-D backbone once on the V frames of a walk-through, voxelises the T = V cumulative clouds as batch entries
+// 0 .. T-1 and fuses, for entry t, views 0 .. t only.  k_point_sample_fwd addresses image (coords[:,0] * V + v) and gives every sample
+// all V views; here a (B, 2) table `win` names, per sample b, the image set s_b its views come from and how many of them, w_b, it
+// sees.  Row i of sample b gets what k_point_sample_fwd<false> writes when launched with V' = w_b on that sample alone (batch column
+// 0, meta row b, feature pointer at set s_b): the same projections, the same f32 terms added in the same ascending view order, the
+// same ballot and division -- bit-identical.  pix keeps its (n, V) shape: columns >= w_b are written -1, so the backward's link pass
+// skips them by the test it already makes.  Same shape as the sibling: one wave per row, 16 rows per workgroup, the meta block
+// (only the w_b matrices in use) staged in LDS when the workgroup's rows share a sample, lane v projects view v; lanes >= w_b
+// neither project nor fetch.  V <= 64 (one ballot).
+template <bool FH>
+__global__ __launch_bounds__(256) void k_point_sample_win_fwd(const int* __restrict__ coords, int n, float voxel_size,
+                                                              const float* __restrict__ meta, int meta_stride, int V,
+                                                              const int* __restrict__ win, const float* __restrict__ feats,
+                                                              int Hf, int Wf, int C, float* __restrict__ out, int ldo,
+                                                              int* __restrict__ pix, int* __restrict__ cnt) {
+  __shared__ float metaS[PS_MAXMETA];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * PS_PTS, i1 = min(n, i0 + PS_PTS);
+  const int b0 = coords[(size_t)i0 * 4], b1 = coords[(size_t)(i1 - 1) * 4];
+  const bool staged = (b0 == b1);                            // workgroup-uniform (32 + 16 * 64 floats always fit)
+  if (staged) {
+    const int nmeta = ES_FUSE_PROJ + 16 * min(max(win[2 * b0 + 1], 0), V);
+    for (int e = threadIdx.x; e < nmeta; e += 256) metaS[e] = meta[(size_t)b0 * meta_stride + e];
+  }
+  __syncthreads();
+  const int MAXC = 8;                                   // supports C <= 512
+  for (int i = i0 + wv; i < i1; i += 4) {               // wave-uniform
+    int4 c = ((const int4*)coords)[i];
+    const int s = win[2 * c.x], w = min(max(win[2 * c.x + 1], 0), V);
+    const float* m = staged ? metaS : meta + (size_t)c.x * meta_stride;
+    float x = __fmul_rn((float)c.y, voxel_size), y = __fmul_rn((float)c.z, voxel_size), z = __fmul_rn((float)c.w, voxel_size);
+    undo_aug(m, x, y, z);
+    bool valid = false;
+    int p = -1;
+    if (lane < w) p = project_view(m, m + ES_FUSE_PROJ + lane * 16, x, y, z, Hf, Wf, valid);
+    if (lane < V) pix[(size_t)i * V + lane] = p;         // -1 beyond the window, always written
+    const int nvalid = (int)__popcll(__ballot(valid));
+    float acc[MAXC];
+#pragma unroll
+    for (int q = 0; q < MAXC; ++q) acc[q] = 0.f;
+    for (int u = 0; u < w; ++u) {                        // views in ascending order: the summation order of the sibling
+      const int pu = __shfl(p, u, 64);
+      if (pu >= 0) {
+        const size_t off = (((size_t)s * V + u) * Hf * Wf + pu) * C;
+#pragma unroll
+        for (int q = 0; q < MAXC; ++q) {
+          int ch = lane + q * 64;                        // sum over ALL views of the window, not masked
+          if (ch < C) acc[q] += FH ? __uint_as_float((uint32_t)((const unsigned short*)feats)[off + ch] << 16) : feats[off + ch];
+        }
+      }
+    }
+    if (lane == 0) cnt[i] = nvalid;
+    float d = (float)max(nvalid, 1);
+#pragma unroll
+    for (int q = 0; q < MAXC; ++q) {
+      int ch = lane + q * 64;
+      if (ch < C) out[(size_t)i * ldo + ch] = nvalid > 0 ? __fdiv_rn(acc[q], d) : 0.f;
+    }
+  }
+}
+extern "C" int es_point_sample_win_fwd(const int* coords, int n, float voxel_size, const float* meta, int meta_stride, int V,
+                                       const int* win, const float* feats, int Hf, int Wf, int C, float* out, int ldo, int* pix,
+                                       int* cnt, void* stream) {
+  if (n <= 0 || V <= 0) return 0;
+  if (C > 512) return -4;
+  if (V > 64) return -9;
+  hipLaunchKernelGGL(k_point_sample_win_fwd<false>, dim3(es_cdiv(n, PS_PTS)), dim3(256), 0, (hipStream_t)stream, coords, n,
+                     voxel_size, meta, meta_stride, V, win, feats, Hf, Wf, C, out, ldo, pix, cnt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_point_sample_win_fwd_h(const int* coords, int n, float voxel_size, const float* meta, int meta_stride, int V,
+                                         const int* win, const void* feats_bf16, int Hf, int Wf, int C, float* out, int ldo,
+                                         int* pix, int* cnt, void* stream) {
+  if (n <= 0 || V <= 0) return 0;
+  if (C > 512) return -4;
+  if (V > 64) return -9;
+  hipLaunchKernelGGL(k_point_sample_win_fwd<true>, dim3(es_cdiv(n, PS_PTS)), dim3(256), 0, (hipStream_t)stream, coords, n,
+                     voxel_size, meta, meta_stride, V, win, (const float*)feats_bf16, Hf, Wf, C, out, ldo, pix, cnt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// Backward of the window fusion: the hit (row i, view v -> pixel p) of a sample with window (s, w) is linked into the list of pixel
+// (s, v, p) when v < w (the forward wrote pix = -1 beyond the window; the test is repeated here so that a pix buffer from elsewhere
+// cannot link outside the window); k_ps_gather then adds dout[i] / cnt[i] per pixel in ascending hit index = ascending row, as
+// es_point_sample_bwd does.  Samples that share a set feed the same pixels.  Every pixel of every set is written.
+__global__ void k_ps_link_win(const int* __restrict__ coords, int n, int V, const int* __restrict__ win,
+                              const int* __restrict__ pix, const int* __restrict__ cnt, int HW, int n_img,
+                              int* __restrict__ head, int* __restrict__ next) {
+  size_t tot = (size_t)n * V;
+  for (size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x; h < tot; h += (size_t)gridDim.x * blockDim.x) {
+    int p = pix[h];
+    if (p < 0) continue;
+    int i = (int)(h / V), v = (int)(h - (size_t)i * V);
+    if (cnt[i] <= 0) continue;       // no valid view in the window: the forward output of this row is 0
+    int b = coords[(size_t)i * 4];
+    int s = win[2 * b];
+    if (v >= win[2 * b + 1] || (long long)s * V + v >= n_img || s < 0) continue;   // outside the window / the gradient buffer
+    next[h] = atomicExch(&head[((size_t)s * V + v) * HW + p], (int)h);
+  }
+}
+extern "C" int es_point_sample_win_bwd(const int* coords, int n, int V, const int* win, const float* dout, int ldo, const int* pix,
+                                       const int* cnt, int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next,
+                                       int accumulate, void* stream) {
+  if (C > 64 * PS_MAXC) return -4;
+  if (V > 64) return -9;
+  const long long n_pix = (long long)n_img * Hf * Wf;
+  if (n_pix <= 0 || V <= 0) return 0;
+  if (n_pix >= (1ll << 31) || (long long)n * V >= (1ll << 31)) return -6;
+  hipStream_t st = (hipStream_t)stream;
+  ES_TRY(hipMemsetAsync(head, 0xff, (size_t)n_pix * sizeof(int), st));
+  if (n > 0) {
+    int g = es_cdiv((long long)n * V, 256);
+    hipLaunchKernelGGL(k_ps_link_win, dim3(g > 8192 ? 8192 : g), dim3(256), 0, st, coords, n, V, win, pix, cnt, Hf * Wf, n_img, head,
+                       next);
+    ES_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_ps_gather, dim3(es_cdiv(n_pix, 4)), dim3(256), 0, st, head, next, (int)n_pix, V, dout, ldo, cnt, C, dfeats,
+                     accumulate);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---- Prefix fusion (continuous occupancy, embodiedscan/models/detectors/embodied_occ.py:165-203) --------------------------
 // The reference builds the image volume of prefix t by calling batch_point_sample on views 0..t, for every t: V (V + 1) / 2
 // view gathers per voxel.  Here ONE pass over the views keeps the running sum and writes the mean of every prefix as it goes:

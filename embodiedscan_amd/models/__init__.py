@@ -7,6 +7,7 @@ from .dense_heads.imvoxel_occ_head import ImVoxelOccHead
 from .dense_heads.grounding_head import GroundingHead
 from .detectors.dense_fusion_occ import DenseFusionOccPredictor
 from .detectors.embodied_occ import EmbodiedOccPredictor
+from .detectors.embodied_det3d import Embodied3DDetector
 from .detectors.sparse_featfusion_grounder import SparseFeatureFusion3DGrounder
 from .necks.mink_neck import MinkNeck
 from .necks.fpn import FPN
@@ -16,4 +17,4 @@ from .detectors.sparse_featfusion_single_stage import SparseFeatureFusionSingleS
 
 __all__ = ['MinkResNet', 'ResNet', 'Det3DDataPreprocessor', 'FCAF3DHeadRotMat',
            'SparseFeatureFusionSingleStage3DDetector', 'ImVoxelOccHead', 'DenseFusionOccPredictor', 'FPN', 'IndoorImVoxelNeck',
-           'AlignedAnchor3DRangeGenerator', 'GroundingHead', 'SparseFeatureFusion3DGrounder', 'MinkNeck', 'EmbodiedOccPredictor']
+           'AlignedAnchor3DRangeGenerator', 'GroundingHead', 'SparseFeatureFusion3DGrounder', 'MinkNeck', 'EmbodiedOccPredictor', 'Embodied3DDetector']

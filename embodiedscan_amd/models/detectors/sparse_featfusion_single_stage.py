@@ -193,10 +193,23 @@ class SparseFeatureFusionSingleStage3DDetector:
     def extract_feat(self, batch_inputs_dict, batch_data_samples):
         """sparse_featfusion_single_stage.py:86-221.  Returns 4 SparseTensors with [3-D | image] channels."""
         self._bind()
+        return self._fuse_points(batch_inputs_dict, batch_data_samples, self._image_feats(batch_inputs_dict['imgs']))
+
+    # per-level projection fusion and its backward: the one point a subclass changes (Embodied3DDetector gives every sample a window
+    # of views instead of all V).  _fuse_level returns what its backward needs; the caller only hands it on.
+    def _fuse_level(self, cs, meta_dev, V, f2d, Hf, Wf, cat, C3):
+        return batch_point_sample_level(cs, self.voxel_size, meta_dev, V, f2d, Hf, Wf, cat, C3)
+
+    def _fuse_level_bwd(self, cs, V, dout, C3, saved, f2d, Hf, Wf):
+        pix, cnt = saved
+        batch_point_sample_level_bwd(cs, V, dout, C3, pix, cnt, f2d, Hf, Wf)
+
+    def _image_feats(self, img):
+        """the 2-D branch of extract_feat: queues the image backbone (on the side stream when forked) -> (feature maps per level, V,
+        (H, W), forked)"""
         # image features first: views folded into the batch dimension (:130-136), channels-last row matrices.  The 2-D
         # backbone needs no host round trip, so its ~10 ms of kernels are queued BEFORE the coordinate pipeline, whose
         # data-dependent row counts force a few stream synchronisations -- those then overlap with the queued work.
-        img = batch_inputs_dict['imgs']
         B, V = img.shape[:2]
         H, W = img.shape[-2:]
         if img.stride(2) != 1:       # (B,V,3,H,W) given NCHW-contiguous: convert once to channels-last
@@ -213,6 +226,11 @@ class SparseFeatureFusionSingleStage3DDetector:
             img_feats = self.backbone(nhwc)
         E.mark('A7 2-D backbone fwd')
         self._tape_marks = [len(E.TAPE.fns)]                   # end of the 2-D backbone's closures
+        return img_feats, V, (H, W), forked
+
+    def _fuse_points(self, batch_inputs_dict, batch_data_samples, image_branch):
+        """the rest of extract_feat: meta table, voxelisation, 3-D backbone, join with the image branch, per-level fusion"""
+        img_feats, V, (H, W), forked = image_branch
         # the projection meta table (pure host arithmetic on the samples' matrices, 1-2 ms for 4 x 20 views) is built HERE, while the
         # device works through the image backbone and before the host waits on the coordinate phase's row counts -- round 4 built it
         # behind the 3-D backbone, where the main stream had run dry: a 0.84 ms hole in every step (profiles/r5i_critical_chain.txt)
@@ -250,10 +268,10 @@ class SparseFeatureFusionSingleStage3DDetector:
             C3, C2 = xl.F.d.shape[1], f2d.d.shape[1]
             cat = torch.empty((xl.cs.n, C3 + C2), dtype=torch.float32, device=self.device)
             E.copy_cols(cat, 0, xl.F.d)
-            pix, cnt = batch_point_sample_level(xl.cs, self.voxel_size, meta_dev, V, f2d, Hf, Wf, cat, C3)
+            saved = self._fuse_level(xl.cs, meta_dev, V, f2d, Hf, Wf, cat, C3)
             y = E.Var(cat)
 
-            def bwd(y=y, xl=xl, f2d=f2d, Hf=Hf, Wf=Wf, pix=pix, cnt=cnt, C3=C3):
+            def bwd(y=y, xl=xl, f2d=f2d, Hf=Hf, Wf=Wf, saved=saved, C3=C3):
                 if y.g is None:
                     return
                 g3 = y.g[:, :C3]
@@ -262,7 +280,7 @@ class SparseFeatureFusionSingleStage3DDetector:
                     E.copy_cols(xl.F.g, 0, g3)
                 else:
                     E.add_into(xl.F.g, g3)
-                batch_point_sample_level_bwd(xl.cs, V, y.g, C3, pix, cnt, f2d, Hf, Wf)
+                self._fuse_level_bwd(xl.cs, V, y.g, C3, saved, f2d, Hf, Wf)
             E.TAPE.add(bwd)
             outs.append(SparseTensor(xl.cs, y))
         E.mark('A8+A9 projection fusion')

@@ -289,6 +289,33 @@ def make_cont_occ_batch(dscan, occ=None):
     return data
 
 
+def make_cont_det_batch(dscan, visible=None):
+    """`data` dict for Embodied3DDetector.train_step from ONE scan of a sweeps pipeline: `points` is the list of the T row-prefix views
+    of the one device cloud (as make_cont_occ_batch), and the single data sample carries list-valued per-prefix `bboxes_3d` /
+    `labels_3d`: prefix t holds the instances visible in any of frames 0 .. t.  Built as ConstructMultiSweeps builds them
+    (multiview.py:192-222), with Python sets -- the box ORDER of a prefix is the iteration order of the running union, so it is the
+    reference's under the same interpreter.  A prefix that sees no instance gets a (0, 9) box tensor.  Det3DDataPreprocessor(
+    batchwise_inputs=True) turns the result into T samples.  visible None: the scan carries `visible_instance_masks` itself."""
+    sl = dscan['points_slice_indices']
+    masks = visible if visible is not None else dscan['visible_instance_masks']
+    assert len(masks) == len(sl) - 1, 'one visibility mask per frame'
+    data = make_batch([dscan])
+    pts = data['inputs']['points'][0]
+    data['inputs']['points'] = [pts[:e] for e in prefix_lengths(sl, pts.shape[0])]
+    boxes = torch.as_tensor(dscan['gt_boxes'], dtype=torch.float32).reshape(-1, 9)
+    labels = torch.as_tensor(dscan['gt_labels'])
+    ids = [set(np.argwhere(np.array(m)).flatten()) for m in masks]
+    cum, per_b, per_l = set(), [], []
+    for t in range(len(masks)):
+        cum = set(ids[0]) if t == 0 else cum.union(ids[t])
+        idx = torch.from_numpy(np.array(list(cum), dtype=np.int32)).long()
+        per_b.append(EulerDepthInstance3DBoxes(boxes[idx]))
+        per_l.append(labels[idx])
+    ds = data['data_samples'][0]
+    ds.gt_instances_3d = InstanceData(bboxes_3d=per_b, labels_3d=per_l)
+    return data
+
+
 def make_grounding_batch(dscans, anns=None):
     """`data` dict for SparseFeatureFusion3DGrounder.train_step: the detection batch with the prompt (`text`), the
     positive character spans (`tokens_positive`) and the TARGET boxes of the prompt as gt_instances_3d.

@@ -269,6 +269,20 @@ int es_point_sample_fwd_pts(const int* coords, const float* points, int n, const
  * caller needs no memset).  n_img = samples * V; head: n_img*Hf*Wf ints, next: n*V ints of scratch. */
 int es_point_sample_bwd(const int* coords, int n, int V, const float* dout, int ldo, const int* pix, const int* cnt,
                         int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next, int accumulate, void* stream);
+/* view-window fusion of the continuous detector (embodied_det3d.py:90-207): win (B,2) int = per sample b the image set s_b its views
+ * come from and the number w_b (1..V) of leading views it sees; feats (n_sets,V,Hf,Wf,C).  The out row and cnt[i] of a row of sample
+ * b equal, bit for bit, what es_point_sample_fwd writes when called with V' = w_b on that sample alone (batch column 0, meta row b,
+ * feats at set s_b); pix (n,V): columns < w_b likewise, columns >= w_b are written -1.  -4: C > 512; -9: V > 64. */
+int es_point_sample_win_fwd(const int* coords, int n, float voxel_size, const float* meta, int meta_stride, int V, const int* win,
+                            const float* feats, int Hf, int Wf, int C, float* out, int ldo, int* pix, int* cnt, void* stream);
+int es_point_sample_win_fwd_h(const int* coords, int n, float voxel_size, const float* meta, int meta_stride, int V, const int* win,
+                              const void* feats_bf16, int Hf, int Wf, int C, float* out, int ldo, int* pix, int* cnt, void* stream);
+/* its backward: dfeats pixel (s, v, p) (+)= sum, in ascending i, of dout[i]/cnt[i] over the rows i of samples with set s and
+ * w_b > v that have cnt[i] > 0 and pix[i,v] = p.  n_img = n_sets * V.  Deterministic gather, every pixel of every set written;
+ * scratch as es_point_sample_bwd. */
+int es_point_sample_win_bwd(const int* coords, int n, int V, const int* win, const float* dout, int ldo, const int* pix,
+                            const int* cnt, int Hf, int Wf, int C, float* dfeats, int n_img, int* head, int* next, int accumulate,
+                            void* stream);
 /* prefix fusion of the continuous occupancy detector (embodied_occ.py:165-203): ONE pass over the V views writes the image
  * volume of every prefix 0..t.  out row t*n + i, columns [0, C) = what es_point_sample_fwd_pts writes to row i when called with
  * t + 1 views, bit for bit (frame-major rows: the batch-major order of the dense neck with B = V); pix (n,V) as the sibling;
