@@ -32,6 +32,22 @@ __host__ __device__ inline void es_unpack(int64_t k, int& b, int& x, int& y, int
   z = (int)(k & ES_FMASK) - ES_OFF;
 }
 
+// Coordinates live in [-ES_OFF, ES_OFF): a neighbour / child / corner outside that range has no key (es_pack would carry
+// into the next field -- another sample's voxel -- or produce ES_EMPTY_KEY); the map kernels report it absent (-1).
+__host__ __device__ inline bool es_in_field(int x, int y, int z) {
+  return x >= -ES_OFF && x < ES_OFF && y >= -ES_OFF && y < ES_OFF && z >= -ES_OFF && z < ES_OFF;
+}
+// f32 quotient -> voxel coordinate: C truncation toward zero for every quotient inside the field (bit-identical to `(int)q`
+// there), saturation to the field's ends beyond it, 0 for NaN (the device conversion's value, spelled out so that a host
+// build agrees).  Keys of garbage / infinite points therefore stay in their own sample and inside the field.
+__host__ __device__ inline int es_quant(float q) {
+  if (!(q == q)) return 0;
+  if (q >= (float)(ES_OFF - 1)) return ES_OFF - 1;
+  if (q <= (float)(-ES_OFF)) return -ES_OFF;
+  return (int)q;
+}
+static inline bool es_cap_ok(int cap, int n) { return cap > 0 && (cap & (cap - 1)) == 0 && cap > n; }
+
 // 64-bit mix (splitmix64 finaliser) -> slot
 __device__ inline uint32_t es_hash(int64_t k, uint32_t mask) {
   uint64_t x = (uint64_t)k;
@@ -44,6 +60,7 @@ __device__ inline uint32_t es_hash(int64_t k, uint32_t mask) {
 // open-addressing lookup: returns value or -1
 __device__ inline int es_table_find(const int64_t* __restrict__ tkeys, const int* __restrict__ tvals,
                                     uint32_t mask, int64_t key) {
+  if (key < 0) return -1;                  // the absent key (es_gen_children_keys) must not match an empty slot and return its fill
   uint32_t s = es_hash(key, mask);
   for (uint32_t it = 0; it <= mask; ++it) {
     int64_t k = tkeys[s];

@@ -13,14 +13,16 @@ __global__ void k_voxel_keys(const float* __restrict__ pts, int n, int ld, int b
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   // TRUE f32 division then C truncation toward zero; never p * (1/vs).
-  int x = (int)__fdiv_rn(pts[(size_t)i * ld + 0], vs);
-  int y = (int)__fdiv_rn(pts[(size_t)i * ld + 1], vs);
-  int z = (int)__fdiv_rn(pts[(size_t)i * ld + 2], vs);
+  // Quotients beyond the coordinate field saturate to its ends, NaN -> 0 (es_quant): every key keeps its own sample index.
+  int x = es_quant(__fdiv_rn(pts[(size_t)i * ld + 0], vs));
+  int y = es_quant(__fdiv_rn(pts[(size_t)i * ld + 1], vs));
+  int z = es_quant(__fdiv_rn(pts[(size_t)i * ld + 2], vs));
   keys[i] = es_pack(batch, x, y, z);
 }
 
 extern "C" int es_voxel_keys(const float* points, int n, int ld, int batch, float voxel_size, int64_t* keys,
                              void* stream) {
+  if (batch < 0 || batch >= ES_MAX_BATCH) return -4;
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_voxel_keys, dim3(es_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, points, n, ld, batch,
                      voxel_size, keys);
@@ -154,6 +156,7 @@ extern "C" int es_unique_first(const int64_t* keys, int n, int64_t* tkeys, int* 
                                int64_t* out_keys, int* out_src, int* count_host, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   *count_host = 0;
+  if (!es_cap_ok(cap, n)) return -4;         // (a full or non-power-of-two table: table_insert_slot would never return)
   ES_TRY(hipMemsetAsync(tkeys, 0xFF, (size_t)cap * 8, st));
   ES_TRY(hipMemsetAsync(tvals, 0x7F, (size_t)cap * 4, st));
   if (n <= 0) return 0;
@@ -184,6 +187,7 @@ __global__ void k_insert_rows(const int64_t* __restrict__ keys, int n, int64_t* 
 // build key -> row table for an already-unique key list
 extern "C" int es_build_table(const int64_t* keys, int n, int64_t* tkeys, int* tvals, int cap, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!es_cap_ok(cap, n)) return -4;
   ES_TRY(hipMemsetAsync(tkeys, 0xFF, (size_t)cap * 8, st));
   ES_TRY(hipMemsetAsync(tvals, 0xFF, (size_t)cap * 4, st));
   if (n <= 0) return 0;
@@ -226,17 +230,20 @@ extern "C" int es_keys_to_coords(const int64_t* keys, int n, int* coords, void* 
   ES_CHECK_LAUNCH();
   return 0;
 }
-__global__ void k_batch_offsets(const int64_t* __restrict__ keys, int n, int nb, int* __restrict__ off) {
-  int b = threadIdx.x;
-  if (b > nb) return;
+__device__ inline int batch_lower_bound(const int64_t* __restrict__ keys, int n, int b) {
   int lo = 0, hi = n;                       // first row with batch >= b (rows are batch-major)
   while (lo < hi) {
     int mid = (lo + hi) >> 1;
     if ((int)(keys[mid] >> (3 * ES_FIELD)) < b) lo = mid + 1; else hi = mid;
   }
-  off[b] = lo;
+  return lo;
+}
+// one workgroup; every offset 0 .. nb is written whatever the workgroup size (nb <= ES_MAX_BATCH)
+__global__ void k_batch_offsets(const int64_t* __restrict__ keys, int n, int nb, int* __restrict__ off) {
+  for (int b = threadIdx.x; b <= nb; b += blockDim.x) off[b] = batch_lower_bound(keys, n, b);
 }
 extern "C" int es_batch_offsets(const int64_t* keys, int n, int n_batch, int* offsets_dev, void* stream) {
+  if (n_batch < 0 || n_batch > ES_MAX_BATCH) return -4;
   hipLaunchKernelGGL(k_batch_offsets, dim3(1), dim3(n_batch + 1 > 64 ? 256 : 64), 0, (hipStream_t)stream, keys, n,
                      n_batch, offsets_dev);
   ES_CHECK_LAUNCH();
@@ -253,19 +260,16 @@ extern "C" int es_batch_offsets(const int64_t* keys, int n, int n_batch, int* of
 // back, their counts and per-sample offsets land in one small device array, and ONE copy + ONE synchronisation brings them to
 // the host.  res layout per level: [count, offsets[0 .. n_batch]].
 __global__ void k_batch_offsets_dev(const int64_t* __restrict__ keys, const int* __restrict__ n_dev, int nb, int* __restrict__ off) {
-  int b = threadIdx.x;
-  if (b > nb) return;
-  int lo = 0, hi = *n_dev;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if ((int)(keys[mid] >> (3 * ES_FIELD)) < b) lo = mid + 1; else hi = mid;
-  }
-  off[b] = lo;
+  const int n = *n_dev;
+  for (int b = threadIdx.x; b <= nb; b += blockDim.x) off[b] = batch_lower_bound(keys, n, b);
 }
 extern "C" int es_strided_chain(const int64_t* root_keys, int n, int n_batch, int n_levels, const int* ts_host,
                                 int64_t* tmp_keys, int* scratch, void** tkeys, void** tvals, const int* caps_host,
                                 void** out_keys, int* res_dev, int* res_host, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (n_batch < 0 || n_batch > ES_MAX_BATCH) return -4;
+  for (int l = 0; l < n_levels; ++l)
+    if (!es_cap_ok(caps_host[l], n)) return -4;           // every level is checked before anything is queued
   const int per = n_batch + 2;
   for (int i = 0; i < n_levels * per; ++i) res_host[i] = 0;
   if (n <= 0 || n_levels <= 0) return 0;
@@ -278,7 +282,6 @@ extern "C" int es_strided_chain(const int64_t* root_keys, int n, int n_batch, in
     int* tv = (int*)tvals[l];
     int64_t* ok = (int64_t*)out_keys[l];
     const int cap = caps_host[l];
-    if (cap <= 0 || (cap & (cap - 1))) return -4;
     const uint32_t mask = (uint32_t)cap - 1;
     int* total = res_dev + l * per;
     ES_TRY(hipMemsetAsync(tk, 0xFF, (size_t)cap * 8, st));
@@ -303,7 +306,9 @@ __global__ void k_gen_children(const int64_t* __restrict__ in, int n, int half, 
   int i = t >> 3, k = t & 7;
   int b, x, y, z;
   es_unpack(in[i], b, x, y, z);
-  out[t] = es_pack(b, x + (k & 1) * half, y + ((k >> 1) & 1) * half, z + ((k >> 2) & 1) * half);
+  int cx = x + (k & 1) * half, cy = y + ((k >> 1) & 1) * half, cz = z + ((k >> 2) & 1) * half;
+  // a child past the end of the field has no key: its row holds ES_EMPTY_KEY (negative: equal to no packed key)
+  out[t] = es_in_field(cx, cy, cz) ? es_pack(b, cx, cy, cz) : ES_EMPTY_KEY;
 }
 extern "C" int es_gen_children_keys(const int64_t* in_keys, int n, int half_ts, int64_t* out_keys, void* stream) {
   if (n <= 0) return 0;
@@ -325,10 +330,13 @@ __global__ void k_kernel_map(const int64_t* __restrict__ out_keys, int n_out, co
   int ox = (k % ksize - c) * in_ts, oy = ((k / ksize) % ksize - c) * in_ts, oz = (k / (ksize * ksize) - c) * in_ts;
   int b, x, y, z;
   es_unpack(out_keys[j], b, x, y, z);
-  nbr[t] = es_table_find(tkeys, tvals, mask, es_pack(b, x + ox, y + oy, z + oz));
+  int nx = x + ox, ny = y + oy, nz = z + oz;
+  // outside the field there is no voxel: never another sample's row (a carry out of the x field), never a table fill value
+  nbr[t] = es_in_field(nx, ny, nz) ? es_table_find(tkeys, tvals, mask, es_pack(b, nx, ny, nz)) : -1;
 }
 extern "C" int es_kernel_map(const int64_t* out_keys, int n_out, const int64_t* tkeys, const int* tvals, int cap,
                              int ksize, int in_ts, int* nbr, void* stream) {
+  if (!es_cap_ok(cap, 0)) return -4;
   if (n_out <= 0) return 0;
   long long tot = (long long)n_out * ksize * ksize * ksize;
   hipLaunchKernelGGL(k_kernel_map, dim3(es_cdiv(tot, 256)), dim3(256), 0, (hipStream_t)stream, out_keys, n_out,
@@ -395,6 +403,7 @@ extern "C" int es_union_plan(const int64_t* keys_a, int na, const int64_t* tkeys
                              const int64_t* keys_b, int nb, const int* a_off_dev, const int* b_off_dev, int n_batch,
                              int* scratch, int* pos_a, int* pos_b, int64_t* out_keys, int* count_host, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!es_cap_ok(cap_a, na > 0 ? na : 0) || n_batch < 0 || n_batch > ES_MAX_BATCH) return -4;
   int* hit = scratch;
   int* isnew = hit + nb;
   int* scan = isnew + nb;
@@ -436,11 +445,13 @@ __global__ void k_interp_map(const int64_t* __restrict__ q, int n, const int64_t
   wk = wk * (sx ? fx : (1.0f - fx));
   wk = wk * (sy ? fy : (1.0f - fy));
   wk = wk * (sz ? fz : (1.0f - fz));
-  idx[t] = es_table_find(tkeys, tvals, mask, es_pack(b, lx + sx * ts, ly + sy * ts, lz + sz * ts));
+  int cx = lx + sx * ts, cy = ly + sy * ts, cz = lz + sz * ts;
+  idx[t] = es_in_field(cx, cy, cz) ? es_table_find(tkeys, tvals, mask, es_pack(b, cx, cy, cz)) : -1;
   w[t] = wk;
 }
 extern "C" int es_interp_map(const int64_t* query_keys, int n, const int64_t* tkeys, const int* tvals, int cap,
                              int table_ts, int* idx, float* w, void* stream) {
+  if (!es_cap_ok(cap, 0)) return -4;
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_interp_map, dim3(es_cdiv((long long)n * 8, 256)), dim3(256), 0, (hipStream_t)stream,
                      query_keys, n, tkeys, tvals, (uint32_t)cap - 1, table_ts, idx, w);

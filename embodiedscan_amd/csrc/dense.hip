@@ -64,18 +64,25 @@ __global__ void k_voxel_keys_range(const float* __restrict__ pts, int n, int ld,
                                    float vx, float vy, float vz, int cx, int cy, int cz, int64_t* __restrict__ keys) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int x = (int)__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 0], mx), vx);
-  int y = (int)__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 1], my), vy);
-  int z = (int)__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 2], mz), vz);
+  // (es_quant: truncation inside the coordinate field, saturation beyond it, NaN -> 0 -- then the clamp)
+  int x = es_quant(__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 0], mx), vx));
+  int y = es_quant(__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 1], my), vy));
+  int z = es_quant(__fdiv_rn(__fsub_rn(pts[(size_t)i * ld + 2], mz), vz));
   x = min(max(x, 0), cx); y = min(max(y, 0), cy); z = min(max(z, 0), cz);
   keys[i] = es_pack(batch, x, y, z);
 }
 extern "C" int es_voxel_keys_range(const float* points, int n, int ld, int batch, const float* rng_host, int64_t* keys,
                                    void* stream) {
+  if (batch < 0 || batch >= ES_MAX_BATCH) return -4;
   if (n <= 0) return 0;
+  int cmax[3];
+  for (int a = 0; a < 3; ++a) {                     // a clamp bound is a coordinate: inside the field
+    cmax[a] = es_quant(rng_host[6 + a]);
+    if (cmax[a] < 0) cmax[a] = 0;
+  }
   hipLaunchKernelGGL(k_voxel_keys_range, dim3(es_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, points, n, ld, batch,
-                     rng_host[0], rng_host[1], rng_host[2], rng_host[3], rng_host[4], rng_host[5], (int)rng_host[6],
-                     (int)rng_host[7], (int)rng_host[8], keys);
+                     rng_host[0], rng_host[1], rng_host[2], rng_host[3], rng_host[4], rng_host[5], cmax[0], cmax[1], cmax[2],
+                     keys);
   ES_CHECK_LAUNCH();
   return 0;
 }

@@ -220,7 +220,7 @@ __global__ void k_plain_keys(const int64_t* __restrict__ keys, int n, uint64_t* 
   idx[i] = i;
 }
 // out_keys / out_src = keys / src permuted into Z-curve order (batch major) -- or, morton = false (es_sort_u64), into ascending
-// order of the keys themselves (non-negative, < 2^62; stable).  scratch: es_sort_scratch_bytes(n).
+// order of the keys themselves (read as unsigned 64-bit, all 8 digits; stable).  scratch: es_sort_scratch_bytes(n).
 static int radix_sort(const int64_t* keys, const int* src, int n, void* scratch, size_t scratch_bytes, int64_t* out_keys, int* out_src,
                       void* stream, bool morton) {
   hipStream_t st = (hipStream_t)stream;
@@ -254,8 +254,8 @@ extern "C" int es_morton_sort(const int64_t* keys, const int* src, int n, void* 
                               int64_t* out_keys, int* out_src, void* stream) {
   return radix_sort(keys, src, n, scratch, scratch_bytes, out_keys, out_src, stream, true);
 }
-// plain ascending stable sort of non-negative 62-bit keys with an int payload (N4: the random-key order of the device-side
-// PointSample draws, data.hip)
+// plain ascending stable sort of 64-bit keys (unsigned order) with an int payload (N4: the random-key order of the device-side
+// PointSample draws, data.hip, whose keys stay below 2^62)
 extern "C" int es_sort_u64(const int64_t* keys, const int* src, int n, void* scratch, size_t scratch_bytes, int64_t* out_keys,
                            int* out_src, void* stream) {
   return radix_sort(keys, src, n, scratch, scratch_bytes, out_keys, out_src, stream, false);

@@ -25,10 +25,25 @@ extern "C" {
 
 #define ES_MAX_SEG 32 /* max samples per batch for segmented (per-sample) operators */
 
-/* ---- coordinate manager (replaces ME.SparseTensor / CoordinateManager) ------------------- */
-/* A4: keys[i] = pack(batch, trunc(p_i / voxel_size)).  sparse_featfusion_single_stage.py:109-116 */
+/* ---- coordinate manager (replaces ME.SparseTensor / CoordinateManager) -------------------
+ * KEYS.  key = sample << 54 | (x + 2^17) << 36 | (y + 2^17) << 18 | (z + 2^17): coordinates lie in [-2^17, 2^17), the sample
+ * index in [0, ES_MAX_BATCH) -- the key is then non-negative (the per-sample offset searches shift it arithmetically) and the
+ * Morton key `sample << 54 | interleave` is injective.  -1 (all bits set) is the empty table slot and the absent key.
+ * EDGE OF THE FIELD.  A neighbour (es_kernel_map), interpolation corner (es_interp_map) or child (es_gen_children_keys) whose
+ * coordinate falls outside the field does not exist: -1 in the maps, the absent key -1 in the child list.  It is never
+ * another sample's voxel and never a table fill value.
+ * TABLES.  (tkeys, tvals, cap): open addressing, cap a power of two and GREATER than the number of keys inserted (the product
+ * uses >= 2n + 2).  Every entry point that takes a cap returns -4, before anything is queued, when cap is not a power of two
+ * or (where the row count is an operand) cap <= n.  First occurrence wins; after es_unique_first the table maps each key to
+ * its unique row.
+ * SAMPLES.  n_batch <= ES_MAX_BATCH (and batch < ES_MAX_BATCH), else -4. */
+#define ES_MAX_BATCH 512 /* sample indices 0 .. 511: the largest for which the packed key stays non-negative */
+/* A4: keys[i] = pack(batch, trunc(p_i / voxel_size)): true f32 division, truncation toward zero.  A quotient beyond the field
+ * saturates to its end (2^17 - 1 / -2^17) and NaN gives 0, so every key unpacks to `batch` and in-field coordinates (a departure
+ * from the reference that needs a point more than 1.3 km from the origin at 1 cm voxels).
+ * sparse_featfusion_single_stage.py:109-116 */
 int es_voxel_keys(const float* points, int n, int ld, int batch, float voxel_size, int64_t* keys, void* stream);
-/* A4: de-duplicate keeping the first occurrence; builds the key->row hash table (cap = power of two >= 2n).
+/* A4: de-duplicate keeping the first occurrence; builds the key->row hash table (cap: power of two > n).
  * scratch: 2n + n/2048 + 4 ints.  Synchronises; *count_host = number of unique keys.
  * sparse_featfusion_single_stage.py:118 (ME.SparseTensor) */
 int es_unique_first(const int64_t* keys, int n, int64_t* tkeys, int* tvals, int cap, int* scratch,
@@ -37,7 +52,8 @@ int es_unique_first(const int64_t* keys, int n, int64_t* tkeys, int* tvals, int 
 size_t es_sort_scratch_bytes(int n);
 int es_morton_sort(const int64_t* keys, const int* src, int n, void* scratch, size_t scratch_bytes, int64_t* out_keys,
                    int* out_src, void* stream);
-/* plain ascending stable sort of non-negative keys < 2^62 with an int payload (same scratch as es_morton_sort) */
+/* plain ascending stable sort with an int payload (same scratch as es_morton_sort): the keys are ordered as UNSIGNED 64-bit
+ * values, all eight 8-bit digits (the product's draw keys stay below 2^62; Morton keys of samples >= 256 do not) */
 int es_sort_u64(const int64_t* keys, const int* src, int n, void* scratch, size_t scratch_bytes, int64_t* out_keys, int* out_src,
                 void* stream);
 /* N4: PointSample._points_random_sampling on the device (datasets/transforms/points.py:155-213: np.random.choice(range(n), k,
@@ -48,24 +64,33 @@ int es_sort_u64(const int64_t* keys, const int* src, int n, void* scratch, size_
 int es_draw_keys(const float* depth, int V, int HW, size_t seed, float* values, int64_t* keys, void* stream);
 int es_draw_keys_index(int n, size_t seed, int stream_id, float* values, int64_t* keys, void* stream);
 int es_draw_unpack(const int64_t* keys, int n, const int* in_view, const int* in_pix, int* out_view, int* out_pix, void* stream);
+/* key -> row table of an already unique key list (cap: power of two > n; empty slots hold key -1 / value -1) */
 int es_build_table(const int64_t* keys, int n, int64_t* tkeys, int* tvals, int cap, void* stream);
 /* strided output coordinates floor(c / ts) * ts.  mink_resnet.py:58-69,104-108 (stride-2 conv / pool) */
 int es_stride_keys(const int64_t* in_keys, int n, int out_ts, int64_t* out_keys, void* stream);
 int es_keys_to_coords(const int64_t* keys, int n, int* coords /* (n,4) b,x,y,z */, void* stream);
 /* points = float(coords[:, 1:]) * voxel_size  (sparse_featfusion_single_stage.py:167-168, fcaf3d_head.py:1145-1147) */
 int es_coords_to_points(const int* coords, int n, float voxel_size, float* points /* (n,3) */, void* stream);
+/* offsets[b] = first row whose sample index is >= b, b = 0 .. n_batch (rows batch-major); n_batch <= ES_MAX_BATCH */
 int es_batch_offsets(const int64_t* keys, int n, int n_batch, int* offsets_dev /* n_batch+1 */, void* stream);
 /* every strided set of the backbone (tensor strides ts[0 .. n_levels-1] of the root set) in one host round trip: each level is
  * the first-occurrence hash-unique of the ROOT keys floored to its stride -- the same rows, row order and key -> row tables as
  * the chain level l -> l+1 that MinkowskiEngine's strided convolutions induce (mink_resnet.py:131-143) -- with its row count and
  * per-sample offsets: res[l * (n_batch + 2)] = count, then n_batch + 1 offsets.  tkeys / tvals / out_keys: host arrays of
- * n_levels device pointers (caps[l] table slots, n rows of keys); tmp_keys n keys; scratch 2n + n/2048 + 8 ints. */
+ * n_levels device pointers (caps[l] table slots -- every caps[l] a power of two greater than n, the ROOT row count, checked for all
+ * levels before anything is queued -- and n rows of keys); tmp_keys n keys; scratch 2n + n/2048 + 8 ints. */
 int es_strided_chain(const int64_t* root_keys, int n, int n_batch, int n_levels, const int* ts_host, int64_t* tmp_keys,
                      int* scratch, void** tkeys, void** tvals, const int* caps_host, void** out_keys, int* res_dev,
                      int* res_host, void* stream);
-/* MinkowskiGenerativeConvolutionTranspose(k=2,s=2) output coordinates.  fcaf3d_head.py:937-941 */
+/* MinkowskiGenerativeConvolutionTranspose(k=2,s=2) output coordinates: out[8 i + k] = parent i + half_ts * (k & 1, k >> 1 & 1,
+ * k >> 2 & 1).  The row layout is positional, so a child past the end of the field cannot be dropped: its row holds the absent
+ * key -1, which is no coordinate set member (parents on multiples of 2 half_ts, as every strided set has them, never produce
+ * one).  A list that holds an absent key is not a coordinate set: the lookups (es_kernel_map, es_interp_map, the probe of
+ * es_union_plan) report a negative key absent, but it must not be INSERTED or placed -- do not pass such a list to
+ * es_unique_first, es_build_table, es_strided_chain, es_batch_offsets or es_union_plan.  fcaf3d_head.py:937-941 */
 int es_gen_children_keys(const int64_t* in_keys, int n, int half_ts, int64_t* out_keys /* 8n */, void* stream);
-/* A6: nbr[j*K + k] = input row at out_j + offset_k * in_ts, or -1 (K = ksize^3, x fastest). */
+/* A6: nbr[j*K + k] = input row at out_j + offset_k * in_ts, or -1 (K = ksize^3, x fastest; offsets -1..1 for ksize 3, 0..1 for
+ * ksize 2).  -1 also when the neighbour coordinate is outside the field. */
 int es_kernel_map(const int64_t* out_keys, int n_out, const int64_t* tkeys, const int* tvals, int cap, int ksize,
                   int in_ts, int* nbr, void* stream);
 int es_inverse_map(const int* nbr, int n_out, int K, int n_in, int* inv /* (n_in,K) */, void* stream);
@@ -396,7 +421,8 @@ int es_volume_map(int n_batch, int X, int Y, int Z, int Xo, int Yo, int Zo, int 
  * dense output voxel (gathered with es_row_move) */
 int es_volume_up_index(int n_batch, int X, int Y, int Z, int* idx, void* stream);
 /* keys = pack(batch, clamp(trunc((p - min) / voxel_size), 0, cmax)); rng_host = 9 HOST floats {min xyz, voxel size xyz,
- * clamp max xyz}.  dense_fusion_occ.py:227-245 */
+ * clamp max xyz}: f32 subtraction, true f32 division, truncation (saturating at the coordinate field, NaN -> 0, as in
+ * es_voxel_keys), then the clamp; cmax itself is limited to the field.  dense_fusion_occ.py:227-245 */
 int es_voxel_keys_range(const float* points, int n, int ld, int batch, const float* rng_host, int64_t* keys, void* stream);
 /* SparseTensor.dense(): idx[i] = dense row ((b*X + x/ts)*Y + y/ts)*Z + z/ts of sparse row i (-1 outside).
  * dense_fusion_occ.py:252-255 */
