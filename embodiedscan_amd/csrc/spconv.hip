@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void k_spconv_wgrad(const float* __restrict__ 
                                             // head kernels instead of 151 -- cost more in lost parallelism, 1.58 -> 1.82 ms per step, than
                                             // it saved in workspace traffic; one slice of a 768^2 x 27 kernel: 2.3 -> 11 ms)
 #define WGRAD_WS_CAP_BIG (256ll << 20)       // weights above 8 M floats (the dense occupancy neck): up to 1 GB, i.e. still 4 .. 8 slices
-struct WgradPlan { int kind, splits, rows_per_split; };   // kind: 0 exact-f32 64x64, 1 bf16 64x64, 2 bf16 128x128, 3 bf16 256x256
+struct WgradPlan { int kind, splits, rows_per_split; };   // kind: 0 exact-f32 64x64, 1 bf16 64x64, 2 bf16 128x128, 3 bf16 256x256, 4 narrow 3 -> 64, 5 k_lin_wgrad_small
 static int cap_splits(int splits, long long dw_floats, bool have_ws) {
   if (!have_ws) return 1;
   long long cap = (dw_floats > (8ll << 20) ? WGRAD_WS_CAP_BIG : ((long long)ES_OPT_WG_CAP_MB << 18)) / (dw_floats > 0 ? dw_floats : 1);
@@ -551,7 +551,9 @@ __global__ __launch_bounds__(256) void k_spconv_narrow_wgrad(const float* __rest
   }
 }
 static WgradPlan wgrad_plan_f32(int n_out, int K, int Cin, int Cout, bool have_ws) {
-  if (ES_OPT_NARROW && K == 27 && Cin == 3 && Cout == 64) {      // (the launcher falls back to one slice of the tiled kernel without a map)
+  // (the plan never sees the map -- es_spconv_wgrad_workspace_floats has none to show it: without a map the launcher runs the tiled kernel
+  //  on THESE slices, whole 64-row tiles and so whole 16-row steps of that kernel; tests/test_gpu_wgrad_kernels.py narrow-plan-no-map-*)
+  if (ES_OPT_NARROW && K == 27 && Cin == 3 && Cout == 64) {
     int splits = cap_splits(es_cdiv(n_out, NW_ROWS) < ES_OPT_NARROW_SLICES ? es_cdiv(n_out, NW_ROWS) : ES_OPT_NARROW_SLICES, (long long)K * Cin * Cout, have_ws);
     int rows_per_split = es_cdiv(es_cdiv(n_out, splits), NW_ROWS) * NW_ROWS;
     return WgradPlan{4, es_cdiv(n_out, rows_per_split), rows_per_split};
@@ -2836,7 +2838,9 @@ static bool lin_wgrad_small_ok(int XH, int YH, const void* X, int ldx, const voi
 static WgradPlan wgrad_plan_bf16(int XH, int YH, const void* X, int ldx, const void* dY, int ldy, int n_out, int n_in, int K,
                                  int Cin, int Cout, bool have_ws) {
   const long long nw = (long long)K * Cin * Cout;
-  if (lin_wgrad_small_ok(XH, YH, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout)) {     // few rows, narrow layers (identity map: the launcher checks)
+  // few rows, narrow layers.  The plan never sees the map: with an explicit map the launcher runs the 64 x 64 gather tile on THESE slices
+  // (whole 256-row blocks, so whole 32-pair chunks and ring refills of that kernel; tests/test_gpu_wgrad_kernels.py lin-plan-identity-map-*)
+  if (lin_wgrad_small_ok(XH, YH, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout)) {
     const int splits = cap_splits(es_cdiv(n_out, LS_KS), nw, have_ws);
     const int rows_per_split = es_cdiv(es_cdiv(n_out, splits), LS_KS) * LS_KS;
     return WgradPlan{5, es_cdiv(n_out, rows_per_split), rows_per_split};

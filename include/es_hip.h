@@ -174,6 +174,8 @@ int es_spconv_fwd_bf16_affine(const void* X, int ldx, const void* W_bf16, const 
 int es_spconv_fwd_bf16_io(const void* X, int x_half, int ldx, const void* W_bf16, const int* nbr, int n_out, int n_in, int K,
                           int Cin, int Cout, const float* scale, const float* shift, const void* res, int res_half, int ldr,
                           int act, void* Y, int y_half, int ldy, void* stream);
+/* h[r][c] = RNE bf16 of x[r][c] (denormals kept, +-0 and +-inf exact, the largest finite f32 -> inf, NaN -> a NaN), h contiguous (n, C);
+ * C odd: -8 before anything is written; C % 8 == 0 with ldx % 4 == 0 and 16-byte aligned x and h take the 16-byte kernel */
 int es_cast_rows_bf16(const float* x, int ldx, int n, int C, void* h /* (n,C) bf16 */, void* stream);
 /* per-step bf16 copies of an f32 [K][A][B] kernel: natural [K][A][B] and/or transposed [K][B][A] (either may be NULL) */
 int es_cast_weight_bf16(const float* w, int K, int A, int B, void* natural, void* transposed, void* stream);
@@ -186,6 +188,22 @@ int es_cast_weights_table(const void* table_dev, int n_entries, int total_tiles,
  * the caller's workspace `ws` ([slice][K][Cin][Cout], es_spconv_wgrad_workspace_floats) and are added to dW in slice order
  * by a second launch.  No float atomics: bit-identical gradients run to run.  ws NULL: ONE slice (correct, under-filled).
  * accumulate 0: dW is OVERWRITTEN (the first gradient a weight receives in a step: no read of dW), 1: added to.
+ * Contracts of the three entry points (tests/wgrad_spec.py, tests/test_gpu_wgrad_kernels.py):
+ *  - value: dW[k] = r(X[nbr[rows_k, k]])^T r(dY[rows_k]), rows_k = {j < n_out: nbr[j, k] >= 0}; nbr NULL: the identity map, rows
+ *    j < min(n_out, n_in) for every tap; r = RNE to bf16 in the bf16 entry points (exact on a shadow), the identity here.  Per
+ *    element |dW - spec| <= 8 u sqrt(pairs of the tap) (|X|^T |dY|) + u (|prior| + |spec|), u = 2^-24;
+ *  - accumulate = 0 overwrites EVERY element of dW (NaN or garbage in it is gone); a tap without a pair gives exact zeros
+ *    (accumulate = 1: the prior bit for bit);
+ *  - the workspace's contents on entry are irrelevant (every partial tile the reduction reads is written first) and unspecified on exit;
+ *  - rows no pair references -- X rows outside the map, dY rows whose taps are all -1 or that lie past n_in on the identity map, the
+ *    ld - C padding columns -- are never interpreted: they may hold NaN (some tiles LOAD X row 0 and the first dY row of a slice
+ *    unconditionally and mask the value, so those rows must be addressable: n_in >= 1);
+ *  - a workspace smaller than es_spconv_wgrad_workspace_floats returns -5 before any launch (dW untouched); n_out, Cin or Cout <= 0
+ *    returns 0 and writes nothing;
+ *  - tile, slices and reduction kernel depend on shapes, strides, operand kinds, pointer alignment and options only -- NOT on the
+ *    map or on whether one is given (the workspace query has no map argument): the narrow 3 -> 64 plan without a map runs the 64 x 64
+ *    f32 tile on the narrow plan's slices, the K = 1 small-row plan with a map runs the bf16 64 x 64 gather tile on that plan's
+ *    slices.  Same arguments -> same launches -> bit-identical dW, run to run.
  * Replaces the backward of MinkowskiConvolution / nn.Conv2d / nn.Linear (mink_resnet.py:58-62, fcaf3d_head.py:907-984). */
 int es_spconv_wgrad(const float* X, int ldx, const float* dY, int ldy, const int* nbr, int n_out, int n_in, int K,
                     int Cin, int Cout, float* dW, int accumulate, float* ws, size_t ws_floats, void* stream);

@@ -194,3 +194,42 @@ def test_checker_rejects_a_bias_gradient_off_in_one_column(emulated, monkeypatch
     b.g[3] += float(100 * FS.G * FS.U * n ** 0.5 * mag[3])
     with pytest.raises(AssertionError, match=r'bias gradient column 3: per-element bound exceeded'):
         TI._check_conv_records(recs, 'emulated linear', torch.device('cpu'))
+
+
+def test_checker_rejects_a_weight_gradient_missing_one_pair(emulated, monkeypatch):
+    """the backward gate's per-element weight-gradient bound: a K = 27 layer whose centre tap has 40 pairs on rows of their own with
+    small output gradients (the rest ~ 3 000 pairs each).  One of those 40 pairs dropped from the launch's result moves that tap's
+    elements by several per cent and the whole tensor by < 2e-4 relative L2: the old assertion passes it, the new one does not"""
+    import test_gpu_insitu as TI
+    from embodiedscan_amd import engine as E
+    monkeypatch.setitem(_ListAsDict(E.PRECISION), 0, 'bf16')
+    monkeypatch.setitem(_ListAsDict(E.HALO), 0, False)
+    monkeypatch.setattr(E, 'DEBUG_CONV', [])
+    g = torch.Generator().manual_seed(13)
+    rng = np.random.default_rng(13)
+    n, cin, cout = 4096, 32, 32
+    nbr = _map(rng, n, n, 27, fill=0.73)
+    nbr[:, 13] = -1
+    own = torch.from_numpy(rng.choice(n, size=40, replace=False))
+    nbr[own] = -1
+    nbr[own, 13] = torch.from_numpy(rng.integers(0, n, size=40).astype(np.int32))
+    w = _param(torch.randn(27, cin, cout, generator=g) / 30, torch.zeros(27, cin, cout))
+    E.TAPE.clear()
+    x = E.Var(torch.randn(n, cin, generator=g), rg=False)
+    y = E.conv(x, w, nbr, None, n)
+    gy = torch.randn(n, cout, generator=g)
+    gy[own] /= 64
+    y.g = gy.clone()
+    E.TAPE.backward()
+    recs = E.DEBUG_CONV
+    assert len(recs) == 1 and recs[0]['w'] is w
+    n_dw, _, _, _ = TI._check_conv_records(recs, 'emulated K = 27 layer', torch.device('cpu'))
+    assert n_dw == 1
+    row = int(own[7])
+    pair = torch.outer(FS._r(x.d[int(nbr[row, 13])]), FS._r(gy[row]))
+    good = w.g.clone()
+    w.g[13] -= pair.float()
+    rel = TI._rel(w.g, good)
+    assert rel < TI.TOL, rel                                      # what the relative L2 alone sees of it
+    with pytest.raises(AssertionError, match=r'weight gradient K=27 32->32 \(1 launch\(es\)\): per-element bound exceeded at dw\[13\]'):
+        TI._check_conv_records(recs, 'emulated K = 27 layer', torch.device('cpu'))

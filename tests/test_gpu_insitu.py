@@ -33,7 +33,9 @@ output cloned right after the launch -- and tests/fwd_spec.py holds each one to 
 over 10^5 rows would pass a few rows that are each 2 % off): convolution / Linear / transposed convolution and the fused epilogues
 to |y - spec| <= 8 u sqrt(n) (|scale| A + |bias|) + u (|shift| + |res|) (+ one bf16 ulp for bf16 rows), A the same gather-GEMM on
 absolute values; every shadow bit-exact.  Every test asserts which entry points it saw, so the gate cannot go quiet when a dispatch
-rule changes.  The backward checker gets the same per-element bound as an additional assertion: data gradients against A and what
+rule changes.  The backward checker gets the same per-element bound as an additional assertion: weight gradients against the sum
+over the launches that feed the weight of u sqrt(pairs of the tap) A (A = the same X^T dY on absolute values) and the running sums they
+round (tests/wgrad_spec.py holds every weight-gradient kernel to the same bound on placed maps), data gradients against A and what
 they accumulated onto, bias gradients per column against sqrt(rows) sum |gy| (the relative-L2 tolerance of a column sum that cancels
 -- the attention key-projection bias -- grows like 1 / |want| and passes anything)."""
 import os
@@ -99,11 +101,45 @@ def _dx_bound(after, want, amag, before, n, label, tag, n_acc=1):
     return float(((err - slack).clamp(min=0)[pos] / lin[pos]).max()) if bool(pos.any()) else 0.0
 
 
+def _dw_mag(x, nbr, n_out, gy, round_fwd, K):
+    """the weight gradient of one launch on absolute values, and the pair count of every tap -> (A (K, cin, cout) f64, n_k (K,) f64)"""
+    xa = (_r(x) if round_fwd else x.double()).abs()
+    ga = (_r(gy) if round_fwd else gy.double()).abs()
+    A = torch.zeros((K, x.shape[1], gy.shape[1]), dtype=torch.float64, device=x.device)
+    nk = torch.zeros(K, dtype=torch.float64, device=x.device)
+    for k in range(K):
+        if nbr is None:
+            rows = src = torch.arange(min(n_out, x.shape[0]), device=x.device)
+        else:
+            rows = torch.nonzero(nbr[:, k] >= 0).squeeze(1)
+            src = nbr[rows, k].long()
+        if rows.numel():
+            A[k] = xa[src].t() @ ga[rows]
+            nk[k] = rows.numel()
+    return A, nk
+
+
+def _dw_bound(got, want, lin, slack, label, tag):
+    """per element (in addition to the relative L2): |dw - want| <= G sum_launches u sqrt(n_k) A + u sum_launches |partial sum| (the
+    form of _dx_bound's n_acc: every launch that adds to the weight's gradient rounds the running sum once); an element no launch
+    contributes to (A = 0) must hold exactly 0 -> the worst ratio (|err| - slack) / sum u sqrt(n_k) A"""
+    err = (got - want).abs()
+    bound = FS.G * lin + slack
+    if bool((~(err <= bound)).any()):
+        i = int(torch.argmax(torch.nan_to_num(err - bound, nan=float('inf')).reshape(-1)))
+        cin, cout = got.shape[-2], got.shape[-1]
+        raise AssertionError(f'{label}: weight gradient {tag}: per-element bound exceeded at dw[{i // (cin * cout)}][{(i // cout) % cin}][{i % cout}]: '
+                             f'got {float(got.reshape(-1)[i]):.8g}, spec {float(want.reshape(-1)[i]):.8g}, |err| '
+                             f'{float(err.reshape(-1)[i]):.3e} > {float(bound.reshape(-1)[i]):.3e} ({int((~(err <= bound)).sum())} elements)')
+    pos = lin > 0
+    return float(((err - slack).clamp(min=0)[pos] / lin[pos]).max()) if bool(pos.any()) else 0.0
+
+
 def _check_conv_records(recs, label, dev):
     """every weight / bias / data gradient of the recorded convolution backwards against _spec; dev: where the
     specification is evaluated (cpu or the GPU, f64 either way)"""
     to = lambda t: None if t is None else t.to(dev)
-    ratio_dx = ratio_db = 0.0
+    ratio_dx = ratio_db = ratio_dw = 0.0
     by_w, by_b = {}, {}
     for r in recs:
         if r['w'].g is not None:
@@ -120,6 +156,7 @@ def _check_conv_records(recs, label, dev):
         K, cin, cout = w.d.shape
         wh = to(w.d.float())
         dw_sum = torch.zeros((K, cin, cout), dtype=torch.float64, device=dev)
+        dw_lin, dw_slack = torch.zeros_like(dw_sum), torch.zeros_like(dw_sum)
         for r in rs:
             seen.add(id(r))
             x, gy = to(r['x'].float()), to(r['gy'].float())
@@ -131,6 +168,9 @@ def _check_conv_records(recs, label, dev):
             amag = _spec(x.abs(), wh.abs(), nbr, r['n_out'], gy.abs(), bf, bf and (cout >= 16 or gate is not None),
                          None if gate is None else gate.abs(), x)[1] if (need_mag or 'group' in r) else None
             dw_sum += dw
+            dw_A, dw_nk = _dw_mag(x, nbr, r['n_out'], gy, bf, K)
+            dw_lin += FS.U * dw_nk.clamp(min=1).sqrt().view(-1, 1, 1) * dw_A
+            dw_slack += FS.U * dw_sum.abs()                       # the running sum after this launch, rounded once
             tag = f'K={K} {cin}->{cout} rows {x.shape[0]}->{r["n_out"]}' + (' gated' if gate is not None else '') + \
                   (' bf16-rows' if r['x'].dtype == torch.bfloat16 else '') + ('' if bf else ' exact-f32') + \
                   (' gen-tap' if 'group' in r else '')
@@ -162,6 +202,8 @@ def _check_conv_records(recs, label, dev):
             if e > worst_dw[0]:
                 worst_dw = (e, f'K={K} {cin}->{cout} ({len(rs)} launch(es))')
             assert e < TOL, f'{label}: weight gradient K={K} {cin}->{cout} ({len(rs)} launches): rel-L2 {e:.2e} (tol {TOL:.0e})'
+        ratio_dw = max(ratio_dw, _dw_bound(to(w.g).double().reshape(K, cin, cout), dw_sum, dw_lin, dw_slack, label,
+                                           f'K={K} {cin}->{cout} ({len(rs)} launch(es))'))
     for g in groups.values():
         assert g['n'] == 8
         if g['need'] and float(g['dx'].norm()) > 0:
@@ -193,8 +235,8 @@ def _check_conv_records(recs, label, dev):
     print(f'{label}: {len(recs)} convolution / Linear backwards, {len(kinds)} launch classes: {n_dw} weight gradients, worst rel-L2 '
           f'{worst_dw[0]:.2e} at {worst_dw[1]}; {n_dx} data gradients, worst {worst_dx[0]:.2e} at {worst_dx[1]}; {n_db} bias '
           f'gradients, worst {worst_db[0]:.2e} at {worst_db[1]} (tol {TOL:.0e} + eps-of-accumulated-buffer)')
-    print(f'{label}: per-element bounds (G = {FS.G:g}): worst data-gradient ratio |err| / (u sqrt(n) A) {ratio_dx:.3f}, worst bias-gradient '
-          f'ratio |err| / (u sqrt(rows) sum|gy|) {ratio_db:.3f}')
+    print(f'{label}: per-element bounds (G = {FS.G:g}): worst weight-gradient ratio |err| / sum (u sqrt(n_k) A) {ratio_dw:.3f}, worst '
+          f'data-gradient ratio |err| / (u sqrt(n) A) {ratio_dx:.3f}, worst bias-gradient ratio |err| / (u sqrt(rows) sum|gy|) {ratio_db:.3f}')
     return n_dw, n_dx, n_db, kinds
 
 
