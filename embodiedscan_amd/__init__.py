@@ -1,0 +1,1 @@
+from . import eval  # noqa: F401  (registers IndoorDetMetric in registry.METRICS)

@@ -11,6 +11,9 @@
 //                           tokens (dense_heads/grounding_head.py:365-425,717-748), value + gradient;
 //   * es_topk_sorted      : per-sample top-k indices in descending score order (query selection,
 //                           detectors/sparse_featfusion_grounder.py:374-376).
+//   * es_det_best_gt / es_det_mark / es_det_ap : IndoorDetMetric on the device (8f row N5; eval/indoor_eval.py:8-182): best
+//                           ground-truth box of every prediction inside its (scene, class) group, TP marking by the lowest
+//                           rank that claims a box, and the area under the precision envelope per (class, threshold).
 // All geometry and the assignment run in f64 (scipy casts the cost matrix to double as well).
 //
 // box3d_overlap: pytorch3d (un-vendored) clips the triangulated faces of each box against the other box and sums
@@ -108,6 +111,170 @@ __global__ void k_box3d_iou(const float* __restrict__ b1, int N, const float* __
 extern "C" int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int M, float* iou, void* stream) {
   if (N <= 0 || M <= 0) return 0;
   hipLaunchKernelGGL(k_box3d_iou, dim3(es_cdiv((long long)N * M, 64)), dim3(64), 0, (hipStream_t)stream, boxes1, N, boxes2, M, iou);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ detection metric (IndoorDetMetric, eval/indoor_eval.py)
+// eval_det_cls:111-132,145-158: one lane per prediction walks the ground-truth boxes of its (scene, class) group in the scene's
+// order.  A prediction with a face below 2e-4 m^2 (f32 products) has its three sizes clamped to 2e-2 first; the IoU is the f64
+// polyhedral one rounded to f32, and the FIRST box that attains the maximum wins (strict >).  No group: iou_max = -inf, gt_best
+// = -1.  No (prediction, box) matrix exists: the work is the number of same-scene same-class pairs.
+__global__ __launch_bounds__(64) void k_box3d_iou_best(const float* __restrict__ pred, int P, const int* __restrict__ pred_grp,
+                                                       const float* __restrict__ gt, const int* __restrict__ grp_off, int n_grp,
+                                                       float* __restrict__ iou_max, int* __restrict__ gt_best) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  float best = -INFINITY;
+  int jbest = -1;
+  const int g = pred_grp[i];
+  if (g >= 0 && g < n_grp) {
+    float p[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) p[c] = pred[(size_t)i * 9 + c];
+    if (p[3] * p[4] < 2e-4f || p[3] * p[5] < 2e-4f || p[5] * p[4] < 2e-4f) {
+      p[3] = fmaxf(p[3], 2e-2f); p[4] = fmaxf(p[4], 2e-2f); p[5] = fmaxf(p[5], 2e-2f);
+    }
+    double a[9], b[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) a[c] = p[c];
+    const int j1 = grp_off[g + 1];
+    for (int j = grp_off[g]; j < j1; ++j) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) b[c] = gt[(size_t)j * 9 + c];
+      const float v = (float)box_iou3d(a, b);
+      if (v > best) { best = v; jbest = j; }
+    }
+  }
+  iou_max[i] = best;
+  gt_best[i] = jbest;
+}
+extern "C" int es_det_best_gt(const float* pred_boxes, int P, const int* pred_grp, const float* gt_boxes, const int* grp_off_dev,
+                              int n_grp, float* iou_max, int* gt_best, void* stream) {
+  if (P < 0 || n_grp < 0) return -5;
+  if (P == 0) return 0;
+  hipLaunchKernelGGL(k_box3d_iou_best, dim3(es_cdiv(P, 64)), dim3(64), 0, (hipStream_t)stream, pred_boxes, P, pred_grp, gt_boxes,
+                     grp_off_dev, n_grp, iou_max, gt_best);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// eval_det_cls:160-168 without the walk down the ranks: at threshold t a ground-truth box goes to the LOWEST rank among the
+// predictions with iou_max > t that point at it (integer atomicMin: the result does not depend on the order of arrival), and a
+// prediction is a true positive iff that rank is its own.  order[r] = prediction at rank r (classes ascending, score descending).
+struct DetThr { float v[ES_DET_MAX_THR]; };
+__global__ void k_det_claim(const float* __restrict__ iou_max, const int* __restrict__ gt_best, const int* __restrict__ order, int P,
+                            DetThr thr, int T, int G, int* __restrict__ claim) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= P) return;
+  const int i = order[r];
+  const int g = gt_best[i];
+  if (g < 0 || g >= G) return;
+  const float v = iou_max[i];
+  for (int t = 0; t < T; ++t)
+    if (v > thr.v[t]) atomicMin(&claim[(size_t)t * G + g], r);
+}
+__global__ void k_det_flag(const float* __restrict__ iou_max, const int* __restrict__ gt_best, const int* __restrict__ order, int P,
+                           DetThr thr, int T, int G, const int* __restrict__ claim, unsigned char* __restrict__ tp) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= P) return;
+  const int i = order[r];
+  const int g = gt_best[i];
+  const float v = iou_max[i];
+  for (int t = 0; t < T; ++t)
+    tp[(size_t)t * P + r] = (g >= 0 && g < G && v > thr.v[t] && claim[(size_t)t * G + g] == r) ? 1 : 0;
+}
+extern "C" int es_det_mark(const float* iou_max, const int* gt_best, const int* order, int P, const float* thr_host, int T, int G,
+                           int* claim, unsigned char* tp, void* stream) {
+  if (P < 0 || G < 0 || T < 1 || T > ES_DET_MAX_THR) return -5;
+  if (P == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  DetThr thr;
+  for (int t = 0; t < ES_DET_MAX_THR; ++t) thr.v[t] = t < T ? thr_host[t] : 0.f;
+  if (G > 0) {
+    ES_TRY(hipMemsetAsync(claim, 0x7f, (size_t)T * G * sizeof(int), st));     // 0x7f7f7f7f: above every rank
+    hipLaunchKernelGGL(k_det_claim, dim3(es_cdiv(P, 256)), dim3(256), 0, st, iou_max, gt_best, order, P, thr, T, G, claim);
+  }
+  hipLaunchKernelGGL(k_det_flag, dim3(es_cdiv(P, 256)), dim3(256), 0, st, iou_max, gt_best, order, P, thr, T, G, claim, tp);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// eval_det_cls:170-180 + average_precision:33-42 for one (class, threshold) per workgroup.  Ranks cls_off[c] .. cls_off[c+1] hold
+// the class's predictions in rank order; every one that is not a TP is an FP, so at position j (0-based) tp + fp = j + 1 and
+//   precision_j = cumtp_j / (j + 1),   recall_j = cumtp_j / npos        (f64 quotients, as numpy forms them).
+// Recall takes a new value exactly at the TPs, so the area is  sum over TPs j of (recall_j - recall_(j-1)) * max_(k >= j)
+// precision_k  (the appended point (1, 0) adds a zero).  Pass 1 counts the TPs; pass 2 walks the chunks of DET_CHUNK ranks from
+// the last to the first with a block scan of the flags (cumtp) and a block suffix maximum (the envelope), carrying the count and
+// the maximum of the later chunks.  The terms are the reference's own f64 values; only the order of the f64 sum differs.
+#define DET_CHUNK 256
+__global__ __launch_bounds__(DET_CHUNK) void k_det_ap(const unsigned char* __restrict__ tp, int P, const int* __restrict__ cls_off,
+                                                      const int* __restrict__ npos, int C, float* __restrict__ ap,
+                                                      int* __restrict__ tp_total) {
+  __shared__ int s_cnt[DET_CHUNK / 64];
+  __shared__ double s_max[DET_CHUNK / 64];
+  __shared__ double s_acc[DET_CHUNK / 64];
+  const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int s = cls_off[c], n = cls_off[c + 1] - s;
+  const unsigned char* f = tp + (size_t)t * P + s;
+  int cnt = 0;
+  for (int j = tid; j < n; j += DET_CHUNK) cnt += f[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if (lane == 0) s_cnt[w] = cnt;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int k = 0; k < DET_CHUNK / 64; ++k) total += s_cnt[k];
+  __syncthreads();
+  const double np = (double)npos[c];
+  int after = 0;               // TPs of the later chunks
+  double env = 0.0;            // highest precision of the later chunks (the appended precision is 0)
+  double acc = 0.0;
+  for (int ch = (n + DET_CHUNK - 1) / DET_CHUNK - 1; ch >= 0; --ch) {
+    const int j = ch * DET_CHUNK + tid;
+    const int flag = j < n ? f[j] : 0;
+    const unsigned long long bal = __ballot(flag);
+    const int incl = __popcll(bal & (~0ull >> (63 - lane)));
+    if (lane == 0) s_cnt[w] = __popcll(bal);
+    __syncthreads();
+    int chunk = 0, before = 0;
+#pragma unroll
+    for (int k = 0; k < DET_CHUNK / 64; ++k) { chunk += s_cnt[k]; if (k < w) before += s_cnt[k]; }
+    const int cum = total - after - chunk + before + incl;          // cumulative TPs up to and including position j
+    double m = j < n ? (double)cum / (double)(j + 1) : 0.0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double v = __shfl_down(m, o, 64);
+      if (lane + o < 64) m = fmax(m, v);
+    }
+    if (lane == 0) s_max[w] = m;
+    __syncthreads();
+    double all = env;
+#pragma unroll
+    for (int k = 0; k < DET_CHUNK / 64; ++k) { all = fmax(all, s_max[k]); if (k > w) m = fmax(m, s_max[k]); }
+    m = fmax(m, env);
+    if (flag) acc += ((double)cum / np - (double)(cum - 1) / np) * m;
+    env = all;
+    after += chunk;
+    __syncthreads();
+  }
+  acc = es_wave_sum_d(acc);
+  if (lane == 0) s_acc[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < DET_CHUNK / 64; ++k) a += s_acc[k];
+    ap[(size_t)t * C + c] = npos[c] > 0 ? (float)a : __builtin_nanf("");     // no ground truth: NaN, as the reference's 0 / 0
+    tp_total[(size_t)t * C + c] = total;
+  }
+}
+extern "C" int es_det_ap(const unsigned char* tp, int P, const int* cls_off_dev, const int* npos_dev, int C, int T, float* ap,
+                         int* tp_total, void* stream) {
+  if (P < 0 || C < 0 || T < 1 || T > ES_DET_MAX_THR) return -5;
+  if (C == 0) return 0;
+  hipLaunchKernelGGL(k_det_ap, dim3(C, T), dim3(DET_CHUNK), 0, (hipStream_t)stream, tp, P, cls_off_dev, npos_dev, C, ap, tp_total);
   ES_CHECK_LAUNCH();
   return 0;
 }

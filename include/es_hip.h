@@ -509,6 +509,21 @@ int es_ground_decode_fcaf_bwd(const float* pred, int ldp, const float* dbox, int
                               void* stream);
 /* N2: exact IoU of 9-DoF Euler (ZXY) boxes, (N,M) -- EulerInstance3DBoxes.overlaps / pytorch3d box3d_overlap */
 int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int M, float* iou, void* stream);
+/* N5: IndoorDetMetric on the device (embodiedscan/eval/indoor_eval.py:8-182).  Ground-truth rows are ordered by (scene, class)
+ * group, grp_off_dev (n_grp+1) delimits the groups, pred_grp (P) is a prediction's group or -1.
+ * es_det_best_gt: predictions with a face below 2e-4 have their sizes clamped to 2e-2; iou_max (P) = the highest f64 polyhedral IoU
+ *   with a box of the group rounded to f32 (-inf without a group), gt_best (P) = the FIRST row that attains it (-1 without).
+ * es_det_mark: order (P) = prediction at each rank (class ascending, score descending); thr_host: T <= ES_DET_MAX_THR host floats.
+ *   claim (T,G) ints of scratch; tp (T,P) u8 BY RANK: 1 iff iou_max > thr (f32 compare) and the rank is the lowest that claims the row.
+ * es_det_ap: cls_off_dev (C+1) rank offsets, npos_dev (C) ground-truth counts -> ap (T,C) f32 (area under the precision envelope,
+ *   summed in f64; NaN where npos = 0) and tp_total (T,C).  -5: a negative count or T outside 1 .. ES_DET_MAX_THR. */
+#define ES_DET_MAX_THR 8
+int es_det_best_gt(const float* pred_boxes, int P, const int* pred_grp, const float* gt_boxes, const int* grp_off_dev, int n_grp,
+                   float* iou_max, int* gt_best, void* stream);
+int es_det_mark(const float* iou_max, const int* gt_best, const int* order, int P, const float* thr_host, int T, int G, int* claim,
+                unsigned char* tp, void* stream);
+int es_det_ap(const unsigned char* tp, int P, const int* cls_off_dev, const int* npos_dev, int C, int T, float* ap, int* tp_total,
+              void* stream);
 /* N2: HungarianAssigner3D for every sample of one decoder layer: costs (BinaryFocalLossCost w_cls, BBox3DL1Cost w_l1,
  * IoU3DCost w_iou) + scipy-compatible rectangular assignment.  logits (B,Q,Tout), boxes (B,Q,9), gt_boxes (sum G,9),
  * pos_map (sum G,T) u8, gt_off_dev (B+1).  cost: B*Gmax*Q doubles, work: B*(Gmax+2Q) doubles, iwork: B*(4Q+2Gmax) ints.
