@@ -279,6 +279,92 @@ extern "C" int es_det_ap(const unsigned char* tp, int P, const int* cls_off_dev,
   return 0;
 }
 
+// ------------------------------------------------------------------ grounding metric (GroundingMetric, grounding_metric.py:70-152)
+// ground_eval:103-110 for a whole batch: lane e = (sample s, slot k) takes the box the sorted top-k put in that slot and walks the
+// sample's ground-truth boxes.  The IoU is the f64 polyhedral one rounded to f32 and compared in f32; there is no thin-box clamp
+// here (the reference calls `overlaps` directly).  `hit[s]` collects one bit per threshold with an integer atomic OR, so the
+// word does not depend on the order in which the slots arrive.  An index outside the sample's rows counts as an empty slot.
+__global__ __launch_bounds__(64) void k_box3d_iou_hits(const float* __restrict__ boxes, const int* __restrict__ box_off,
+                                                       const int* __restrict__ topk, int S, int K, const float* __restrict__ gt,
+                                                       const int* __restrict__ gt_off, DetThr thr, int T, int* __restrict__ hit,
+                                                       float* __restrict__ iou_top) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S * K) return;
+  const int s = e / K;
+  const int q = topk[e];
+  const int q0 = box_off[s], nq = box_off[s + 1] - q0;
+  float best = -INFINITY;
+  int bits = 0;
+  if (q >= 0 && q < nq) {
+    double a[9], b[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) a[c] = boxes[(size_t)(q0 + q) * 9 + c];
+    const int j1 = gt_off[s + 1];
+    for (int j = gt_off[s]; j < j1; ++j) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) b[c] = gt[(size_t)j * 9 + c];
+      const float v = (float)box_iou3d(a, b);
+      best = fmaxf(best, v);
+      for (int t = 0; t < T; ++t)
+        if (v > thr.v[t]) bits |= 1 << t;
+    }
+  }
+  iou_top[e] = best;
+  if (bits) atomicOr(&hit[s], bits);
+}
+extern "C" int es_ground_hits(const float* boxes, const int* box_off_dev, const int* topk_idx, int S, int K, const float* gt_boxes,
+                              const int* gt_off_dev, const float* thr_host, int T, int* hit, float* iou_top, void* stream) {
+  if (S < 0 || K < 0 || T < 1 || T > ES_DET_MAX_THR || (long long)S * K > 0x7fffffffLL) return -5;
+  if (S == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  ES_TRY(hipMemsetAsync(hit, 0, (size_t)S * sizeof(int), st));
+  if (K == 0) return 0;
+  DetThr thr;
+  for (int t = 0; t < ES_DET_MAX_THR; ++t) thr.v[t] = t < T ? thr_host[t] : 0.f;
+  hipLaunchKernelGGL(k_box3d_iou_hits, dim3(es_cdiv((long long)S * K, 64)), dim3(64), 0, st, boxes, box_off_dev, topk_idx, S, K,
+                     gt_boxes, gt_off_dev, thr, T, hit, iou_top);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// ground_eval:108-131 over the gathered samples: every sample counts in Overall and in one type of each pair.  Types in the
+// reference's order: 0 Easy, 1 Hard, 2 View-Dep, 3 View-Indep, 4 Unique, 5 Multi, 6 Overall.  counts (T,7,2) = [found, samples].
+// Each workgroup counts in LDS (integer atomics) and flushes its non-zero counters with one integer atomic each.
+#define GT_TYPES 7
+__global__ __launch_bounds__(256) void k_ground_tally(const int* __restrict__ hit, const unsigned char* __restrict__ flags, int N,
+                                                      int T, int* __restrict__ counts) {
+  __shared__ int s_found[ES_DET_MAX_THR * GT_TYPES];
+  __shared__ int s_n[GT_TYPES];
+  for (int i = threadIdx.x; i < ES_DET_MAX_THR * GT_TYPES; i += blockDim.x) s_found[i] = 0;
+  if (threadIdx.x < GT_TYPES) s_n[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    const int f = flags[i], h = hit[i];
+    const int ty[4] = {(f & 2) ? 1 : 0, (f & 1) ? 2 : 3, (f & 4) ? 4 : 5, 6};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) atomicAdd(&s_n[ty[k]], 1);
+    for (int t = 0; t < T; ++t)
+      if ((h >> t) & 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) atomicAdd(&s_found[t * GT_TYPES + ty[k]], 1);
+      }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < T * GT_TYPES; i += blockDim.x) {
+    if (s_found[i]) atomicAdd(&counts[i * 2], s_found[i]);
+    if (s_n[i % GT_TYPES]) atomicAdd(&counts[i * 2 + 1], s_n[i % GT_TYPES]);
+  }
+}
+extern "C" int es_ground_tally(const int* hit, const unsigned char* flags, int N, int T, int* counts, void* stream) {
+  if (N < 0 || T < 1 || T > ES_DET_MAX_THR) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  ES_TRY(hipMemsetAsync(counts, 0, (size_t)T * GT_TYPES * 2 * sizeof(int), st));
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(k_ground_tally, dim3(min(es_cdiv(N, 256), 256)), dim3(256), 0, st, hit, flags, N, T, counts);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ matching costs
 // cost[b][g][q] (G rows, Q columns: the orientation scipy's solver works in after its own transpose, nr <= nc)
 __global__ void k_ground_cost(const float* __restrict__ logits, int Tout, const float* __restrict__ boxes, int Q,

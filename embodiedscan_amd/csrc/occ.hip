@@ -248,3 +248,53 @@ extern "C" int es_occ_loss(const float* logits, int ld, const int* gt, int n, in
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------ evaluation (OccupancyMetric, occupancy_metric.py:76-90)
+// Confusion counts of one volume: over the voxels with gt != 255, row j >= 1 = [gt == j & pred == j, gt == j, pred == j] and row 0
+// (geometry) the same with `!= 0`.  A label outside 0 .. C-1 is never `== j`, so it counts in row 0 only.  Row 0 is counted in
+// registers and reduced over the wave; the class rows are a 3*C-counter histogram in LDS.  Both are flushed with integer
+// atomics into the row the launcher zeroed: the result does not depend on the order of arrival.
+#define OCC_CONF_MAXWG 128
+__global__ __launch_bounds__(256) void k_occ_confusion(const long long* __restrict__ pred, const int* __restrict__ gt, int n, int C,
+                                                       int* __restrict__ counts) {
+  __shared__ int s_cnt[3 * OCC_MAXC];
+  for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) s_cnt[i] = 0;
+  __syncthreads();
+  int both = 0, ng = 0, np = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int g = gt[i];
+    if (g == 255) continue;
+    const long long p = pred[i];
+    ng += g != 0;
+    np += p != 0;
+    both += (g != 0) && (p != 0);
+    const bool gin = g >= 1 && g < C, pin = p >= 1 && p < C;
+    if (gin) atomicAdd(&s_cnt[3 * g + 1], 1);
+    if (pin) atomicAdd(&s_cnt[3 * (int)p + 2], 1);
+    if (gin && p == g) atomicAdd(&s_cnt[3 * g], 1);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    both += __shfl_xor(both, o, 64);
+    ng += __shfl_xor(ng, o, 64);
+    np += __shfl_xor(np, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (both) atomicAdd(&s_cnt[0], both);
+    if (ng) atomicAdd(&s_cnt[1], ng);
+    if (np) atomicAdd(&s_cnt[2], np);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * C; i += blockDim.x)
+    if (s_cnt[i]) atomicAdd(&counts[i], s_cnt[i]);
+}
+extern "C" int es_occ_confusion(const long long* pred, const int* gt, int n, int C, int* counts, void* stream) {
+  if (C > OCC_MAXC || C < 1) return -4;
+  if (n < 0) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  ES_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (size_t)(3 * C), st));
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_occ_confusion, dim3(min(es_cdiv(n, 256), OCC_CONF_MAXWG)), dim3(256), 0, st, pred, gt, n, C, counts);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

@@ -524,6 +524,24 @@ int es_det_mark(const float* iou_max, const int* gt_best, const int* order, int 
                 unsigned char* tp, void* stream);
 int es_det_ap(const unsigned char* tp, int P, const int* cls_off_dev, const int* npos_dev, int C, int T, float* ap, int* tp_total,
               void* stream);
+/* N6: GroundingMetric on the device (embodiedscan/eval/metrics/grounding_metric.py:70-152).
+ * es_ground_hits: one launch per processed batch of S samples.  boxes: the samples' predicted boxes concatenated, box_off_dev (S+1);
+ *   topk_idx (S,K): rows LOCAL to the sample as es_topk_sorted writes them (-1 or a row outside the sample: an empty slot);
+ *   gt_boxes concatenated, gt_off_dev (S+1); thr_host: T <= ES_DET_MAX_THR host floats.  One lane per (sample, slot) walks the
+ *   sample's ground-truth boxes: f64 polyhedral IoU rounded to f32, NO thin-box clamp.  hit (S): bit t set iff some IoU of the
+ *   sample > thr[t] (f32 compare; zeroed by the call, combined with an integer atomic OR); iou_top (S,K): the slot's highest IoU,
+ *   -inf for an empty slot or a sample without ground truth.
+ * es_ground_tally: hit (N), flags (N) u8 {bit 0 view-dependent, bit 1 hard, bit 2 unique} -> counts (T,7,2) int32 [found, samples]
+ *   over the types Easy, Hard, View-Dep, View-Indep, Unique, Multi, Overall (zeroed by the call; integer atomics only).
+ * -5, with every output untouched: a negative count or T outside 1 .. ES_DET_MAX_THR. */
+int es_ground_hits(const float* boxes, const int* box_off_dev, const int* topk_idx, int S, int K, const float* gt_boxes,
+                   const int* gt_off_dev, const float* thr_host, int T, int* hit, float* iou_top, void* stream);
+int es_ground_tally(const int* hit, const unsigned char* flags, int N, int T, int* counts, void* stream);
+/* N6: OccupancyMetric's confusion counts of one volume (embodiedscan/eval/metrics/occupancy_metric.py:76-90): pred (n) int64, gt (n)
+ * int32 (es_occ_targets at ratio 1; 255 = ignored) -> counts (C,3) int32, zeroed by the call: over the voxels with gt != 255, row
+ * j >= 1 = [gt == j and pred == j, gt == j, pred == j], row 0 the same with `!= 0` in place of `== j`; a label outside 0 .. C-1 counts
+ * in row 0 only.  -4: C outside 1 .. 256; -5: n < 0; nothing is written then. */
+int es_occ_confusion(const long long* pred, const int* gt, int n, int C, int* counts, void* stream);
 /* N2: HungarianAssigner3D for every sample of one decoder layer: costs (BinaryFocalLossCost w_cls, BBox3DL1Cost w_l1,
  * IoU3DCost w_iou) + scipy-compatible rectangular assignment.  logits (B,Q,Tout), boxes (B,Q,9), gt_boxes (sum G,9),
  * pos_map (sum G,T) u8, gt_off_dev (B+1).  cost: B*Gmax*Q doubles, work: B*(Gmax+2Q) doubles, iwork: B*(4Q+2Gmax) ints.
