@@ -806,3 +806,237 @@ extern "C" int es_ground_decode_fcaf_bwd(const float* pred, int ldp, const float
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------ frozen RoBERTa text encoder (forward only; embodiedscan_amd/text.py
+// HipTextEncoder): embedding gather + position rule + LayerNorm, residual LayerNorm up to C = 1024, exact-erf bias + GELU, and a masked
+// self-attention with head dimension 64 on a packed [q | k | v] projection.  The projections themselves are K = 1 row GEMMs.
+#define TX_MAXQ 16       // channels per lane of a row held by one wave: C <= 64 * TX_MAXQ = 1024
+
+// y[c] = (v - mean) * rstd * w[c] + b[c] for the row a wave holds as v[q] = row[lane + 64 q] (k_ln_fwd's arithmetic: two passes)
+__device__ inline void tx_ln_row(const float (&v)[TX_MAXQ], int C, int lane, const float* __restrict__ w, const float* __restrict__ bia,
+                                 float eps, float* __restrict__ yrow) {
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < TX_MAXQ; ++q) if (lane + q * 64 < C) s += v[q];
+  const float mu = es_wave_sum(s) / (float)C;
+  float ss = 0.f;
+#pragma unroll
+  for (int q = 0; q < TX_MAXQ; ++q) if (lane + q * 64 < C) { float d = v[q] - mu; ss += d * d; }
+  const float rs = rsqrtf(es_wave_sum(ss) / (float)C + eps);
+#pragma unroll
+  for (int q = 0; q < TX_MAXQ; ++q) {
+    const int c = lane + q * 64;
+    if (c < C) yrow[c] = (v[q] - mu) * rs * w[c] + bia[c];
+  }
+}
+
+// One wave per token row (b, t).  ids outside [0, vocab) count as pad_id everywhere.  Position (modeling_roberta.py
+// create_position_ids_from_input_ids): pad_id + (id != pad_id ? #{t' <= t : id[t'] != pad_id} : 0).
+__global__ __launch_bounds__(256) void k_text_embed_ln(const long long* __restrict__ ids, int n, int T, int pad_id,
+                                                       const float* __restrict__ word, const float* __restrict__ pos,
+                                                       const float* __restrict__ type0, int C, int vocab, const float* __restrict__ w,
+                                                       const float* __restrict__ bia, float eps, float* __restrict__ y,
+                                                       int* __restrict__ pos_ids) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  const int t = i % T;
+  const long long* row = ids + (size_t)(i - t);
+  int cnt = 0;
+  for (int u = lane; u <= t; u += 64) {
+    const long long v = row[u];
+    cnt += (v >= 0 && v < vocab && v != pad_id) ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  long long id = row[t];
+  if (id < 0 || id >= vocab) id = pad_id;
+  const int p = pad_id + (id != pad_id ? cnt : 0);         // <= pad_id + T < max_pos (checked by the entry point)
+  if (pos_ids && lane == 0) pos_ids[i] = p;
+  const float* wr = word + (size_t)id * C;
+  const float* pr = pos + (size_t)p * C;
+  float v[TX_MAXQ];
+#pragma unroll
+  for (int q = 0; q < TX_MAXQ; ++q) {
+    const int c = lane + q * 64;
+    v[q] = c < C ? (wr[c] + pr[c]) + type0[c] : 0.f;
+  }
+  tx_ln_row(v, C, lane, w, bia, eps, y + (size_t)i * C);
+}
+extern "C" int es_text_embed_ln(const long long* ids, int B, int T, int pad_id, const float* word, const float* pos,
+                                const float* type0, int C, int vocab, int max_pos, const float* ln_w, const float* ln_b, float eps,
+                                float* y, int* pos_ids, void* stream) {
+  if (B <= 0 || T <= 0) return 0;
+  if (!ids || !word || !pos || !type0 || !ln_w || !ln_b || !y) return -4;
+  if (C <= 0 || C > 64 * TX_MAXQ || vocab <= 0 || pad_id < 0 || pad_id >= vocab) return -4;
+  if ((long long)pad_id + T >= max_pos || (long long)B * T > 0x7fffffffLL) return -4;
+  const int n = B * T;
+  hipLaunchKernelGGL(k_text_embed_ln, dim3(es_cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, ids, n, T, pad_id, word, pos, type0, C,
+                     vocab, ln_w, ln_b, eps, y, pos_ids);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// y = LayerNorm(x (+ res)) for C <= 1024, no saved statistics (es_layernorm_fwd stops at 512 and feeds a backward pass).  A wave
+// holds its whole row before it writes: y may alias x or res.
+__global__ __launch_bounds__(256) void k_text_add_ln(const float* x, const float* res, int n, int C, const float* __restrict__ w,
+                                                     const float* __restrict__ bia, float eps, float* y) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  float v[TX_MAXQ];
+#pragma unroll
+  for (int q = 0; q < TX_MAXQ; ++q) {
+    const int c = lane + q * 64;
+    v[q] = 0.f;
+    if (c < C) v[q] = x[(size_t)i * C + c] + (res ? res[(size_t)i * C + c] : 0.f);
+  }
+  tx_ln_row(v, C, lane, w, bia, eps, y + (size_t)i * C);
+}
+extern "C" int es_text_add_ln(const float* x, const float* res, int n, int C, const float* w, const float* b, float eps, float* y,
+                              void* stream) {
+  if (n <= 0) return 0;
+  if (!x || !w || !b || !y || C <= 0 || C > 64 * TX_MAXQ) return -4;
+  hipLaunchKernelGGL(k_text_add_ln, dim3(es_cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, x, res, n, C, w, b, eps, y);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// x[r, c] <- gelu(x[r, c] + bias[c]), the exact form 0.5 z (1 + erf(z / sqrt 2)) (transformers' "gelu"), in place, c < C of rows with
+// leading dimension ld
+__global__ void k_bias_gelu(float* __restrict__ x, int ld, int n, int C, const float* __restrict__ bias) {
+  const size_t total = (size_t)n * C;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = e / C;
+    const int c = (int)(e - r * C);
+    float* p = x + r * ld + c;
+    const float z = *p + bias[c];
+    *p = (0.5f * z) * (1.f + erff(z * 0.70710678118654752f));
+  }
+}
+extern "C" int es_bias_gelu(float* x, int ld, int n, int C, const float* bias, void* stream) {
+  if (n <= 0) return 0;
+  if (!x || !bias || C <= 0 || ld < C) return -4;
+  hipLaunchKernelGGL(k_bias_gelu, dim3(min(es_cdiv((long long)n * C, 256), 4096)), dim3(256), 0, (hipStream_t)stream, x, ld, n, C,
+                     bias);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// Self-attention with head dimension 64 on the packed projection: row (b T + t) holds [q | k | v], head h in columns 64 h .. of
+// each third.  Prompts are short (T = 10 .. 40) and B H is large, so the unit of work is ONE WAVE = one (sample, head, 16-query
+// tile), launched as a one-wave workgroup: nothing is shared between waves, a barrier costs nothing, and the chip sees
+// B H ceil(T / 16) independent workgroups (several per CU: 22.5 KiB of LDS in bf16, 40.6 KiB in f32).  Keys are walked in steps
+// of 64 with the online softmax; for T <= 64 that is one step, the whole K and V^T of the (sample, head) resident in LDS.
+// A score tile (16 queries x 16 keys) is two 16x16x32 k-steps.  mask: (B, T) int32, 0 = key masked (any pattern), NULL = all live.
+#define TA_D 64
+#define TA_KS 64
+template <bool BF> struct TaT;
+template <> struct TaT<true> { static constexpr int LD = 72; };       // 144-byte rows: the 16-byte fragments stay aligned
+template <> struct TaT<false> { static constexpr int LD = 65; };
+
+template <bool BF>
+__global__ __launch_bounds__(64) void k_text_attn_fwd(const float* __restrict__ qkv, int ld, int H, int T,
+                                                      const int* __restrict__ mask, float* __restrict__ O, int ldo, int nqt) {
+  typedef typename AtT<BF>::T S;
+  constexpr int LD = TaT<BF>::LD;
+  __shared__ __attribute__((aligned(16))) S Qs[16 * LD], Ks[TA_KS * LD], Vt[TA_D * LD], Ps[16 * LD];
+  const int item = blockIdx.x;
+  const int qt = item % nqt, h = (item / nqt) % H, b = item / (nqt * H);
+  const int lane = threadIdx.x, li = lane & 15, kq = lane >> 4;
+  const int q0 = qt * 16, E = H * TA_D;
+  const float* base = qkv + (size_t)b * T * ld + h * TA_D;
+  const int* mrow = mask ? mask + (size_t)b * T : nullptr;
+  for (int e = lane; e < 16 * 16; e += 64) {               // Q tile, scaled by 1/8 (a power of two: commutes with the rounding)
+    const int r = e >> 4, c = (e & 15) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q0 + r < T) v = *(const float4*)(base + (size_t)(q0 + r) * ld + c);
+    S* d = Qs + r * LD + c;
+    d[0] = at_cvt<BF>(v.x * 0.125f); d[1] = at_cvt<BF>(v.y * 0.125f); d[2] = at_cvt<BF>(v.z * 0.125f); d[3] = at_cvt<BF>(v.w * 0.125f);
+  }
+  float m[4], l[4];
+  tf32x4_t o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; o[r] = (tf32x4_t){0.f, 0.f, 0.f, 0.f}; }
+  for (int k0 = 0; k0 < T; k0 += TA_KS) {
+    __syncthreads();                                       // the previous step's readers of Ks / Vt / Ps are done
+    for (int e = lane; e < TA_KS * 16; e += 64) {
+      const int r = e >> 4, c = (e & 15) * 4;
+      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+      if (k0 + r < T) {
+        const float* p = base + (size_t)(k0 + r) * ld + c;
+        kv = *(const float4*)(p + E);
+        vv = *(const float4*)(p + 2 * E);
+      }
+      S* d = Ks + r * LD + c;
+      d[0] = at_cvt<BF>(kv.x); d[1] = at_cvt<BF>(kv.y); d[2] = at_cvt<BF>(kv.z); d[3] = at_cvt<BF>(kv.w);
+      Vt[(c + 0) * LD + r] = at_cvt<BF>(vv.x);
+      Vt[(c + 1) * LD + r] = at_cvt<BF>(vv.y);
+      Vt[(c + 2) * LD + r] = at_cvt<BF>(vv.z);
+      Vt[(c + 3) * LD + r] = at_cvt<BF>(vv.w);
+    }
+    __syncthreads();
+    tf32x4_t s[4];
+    bool ok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      s[t] = (tf32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) s[t] = tile_mma<BF>(Qs + li * LD + ks * 32, Ks + (t * 16 + li) * LD + ks * 32, kq, s[t]);
+      const int j = k0 + t * 16 + li;
+      ok[t] = j < T && (!mrow || mrow[j] != 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float sv[4], mx = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { sv[t] = ok[t] ? s[t][r] : -INFINITY; mx = fmaxf(mx, sv[t]); }
+      mx = group16_max(mx);
+      const float mn = fmaxf(m[r], mx);
+      const float ref = mn == -INFINITY ? 0.f : mn;        // no live key so far: every exponential below is exp(-inf) = 0
+      const float corr = BF ? __expf(m[r] - ref) : expf(m[r] - ref);
+      float ps = 0.f;
+      S* prow = Ps + (kq * 4 + r) * LD;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float p = BF ? __expf(sv[t] - ref) : expf(sv[t] - ref);
+        ps += p;
+        prow[t * 16 + li] = at_cvt<BF>(p);
+      }
+      l[r] = l[r] * corr + group16_sum(ps);
+      m[r] = mn;
+#pragma unroll
+      for (int nf = 0; nf < 4; ++nf) o[nf][r] *= corr;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) o[nf] = tile_mma<BF>(Ps + li * LD + ks * 32, Vt + (nf * 16 + li) * LD + ks * 32, kq, o[nf]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = q0 + kq * 4 + r;
+    if (q >= T) continue;
+    const float inv = l[r] > 0.f ? 1.f / l[r] : 0.f;       // a sample without a live key: O = 0 (the file's convention, k_attn_fwd)
+    float* orow = O + ((size_t)b * T + q) * ldo + h * TA_D;
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf) orow[nf * 16 + li] = o[nf][r] * inv;
+  }
+}
+extern "C" int es_text_attn_fwd(const float* qkv, int ld, int B, int H, int T, const int* mask_dev, float* O, int ldo, int bf16,
+                                void* stream) {
+  if (B <= 0 || H <= 0) return 0;
+  if (!qkv || !O || T < 1 || T > 512) return -4;
+  if ((long long)H * TA_D * 3 > ld || (long long)H * TA_D > ldo || ((ld | ldo) & 3)) return -4;
+  if (((size_t)qkv & 15) != 0) return -4;                  // rows are read as float4
+  const int nqt = es_cdiv(T, 16);
+  const long long items = (long long)B * H * nqt;
+  if (items > 0x7fffffffLL || (long long)B * T > 0x7fffffffLL) return -4;
+  if (bf16)
+    hipLaunchKernelGGL(k_text_attn_fwd<true>, dim3((unsigned)items), dim3(64), 0, (hipStream_t)stream, qkv, ld, H, T, mask_dev, O, ldo,
+                       nqt);
+  else
+    hipLaunchKernelGGL(k_text_attn_fwd<false>, dim3((unsigned)items), dim3(64), 0, (hipStream_t)stream, qkv, ld, H, T, mask_dev, O, ldo,
+                       nqt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

@@ -10,7 +10,7 @@ from ... import hip
 from ...hip import P, call
 from ...params import ParamArena, grounder_specs
 from ...registry import MODELS
-from ...text import HashTokenizer, TextGraph, build_text_encoder, create_positive_map
+from ...text import HashTokenizer, HipTextEncoder, TextGraph, build_text_encoder, create_positive_map
 from ..layers.ground_transformer.decoder import SparseFeatureFusionTransformerDecoder, _Lin
 from .sparse_featfusion_single_stage import SparseFeatureFusionSingleStage3DDetector
 
@@ -25,7 +25,7 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
     def __init__(self, backbone, backbone_3d, bbox_head, neck=None, neck_3d=None, decoder=None, voxel_size=0.01,
                  num_queries=512, max_num_entities=256, coord_type='CAMERA', train_cfg=None, test_cfg=None,
                  data_preprocessor=None, use_xyz_feat=False, init_cfg=None, seed=0, device='cuda:0', text_encoder_cfg=None,
-                 tokenizer=None):
+                 tokenizer=None, text_encoder_impl=None):
         assert neck is None and neck_3d is not None and decoder is not None
         self.device = torch.device(device)
         self.backbone = MODELS.build(backbone)
@@ -44,7 +44,14 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         self.voxel_size, self.use_xyz_feat = voxel_size, use_xyz_feat
         # text side (roberta-base vocabulary / weights are not available offline: stand-ins, see text.py)
         self.tokenizer = tokenizer or HashTokenizer()
+        # 'torch': transformers' module, run by torch; 'hip': the same seeded module converted to text.HipTextEncoder and dropped (both
+        # start from identical weights).  Not given: ES_TEXT_ENCODER decides, unset means 'torch'.
+        self.text_encoder_impl = text_encoder_impl or os.environ.get('ES_TEXT_ENCODER') or 'torch'
+        if self.text_encoder_impl not in ('torch', 'hip'):
+            raise ValueError(f"text_encoder_impl must be 'torch' or 'hip', got {self.text_encoder_impl!r}")
         self.text_encoder = build_text_encoder(text_encoder_cfg, seed=seed)
+        if self.text_encoder_impl == 'hip':
+            self.text_encoder = HipTextEncoder.from_module(self.text_encoder)
         self.text_dim = self.text_encoder.config.hidden_size
         self.arena = ParamArena(grounder_specs(text_dim=self.text_dim, E=self.embed_dims, num_layers=self.decoder.num_layers,
                                                ffn=self.decoder.ffn_channels, in_channels=self.neck_3d.in_channels), seed=seed)
@@ -105,6 +112,8 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         # (buffers such as embeddings.position_ids exist or not depending on the transformers version: never "missing")
         params = {k for k, _ in self.text_encoder.named_parameters()}
         missing = list(missing) + [pre + k for k in own if k not in text and k in params]
+        if self.text_encoder_impl == 'hip':
+            self.text_encoder.refresh()          # the fused / bf16 kernel-layout copies follow the loaded weights
         if strict and (missing or unexpected):
             raise RuntimeError(f'load_state_dict: missing {missing[:5]}... unexpected {unexpected[:5]}...')
         return missing, unexpected
@@ -143,7 +152,10 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
             tok = tok.to(self.device)
             with torch.no_grad():
                 B, T = tok.input_ids.shape
-                hs = self._encode_graph(tok, B, T) if (side and TEXT_GRAPH[0]) else None
+                if self.text_encoder_impl == 'hip':      # any (B, T) on the same ~ 100 launches: no graph, no shape cache
+                    hs = self.text_encoder(tok.input_ids, tok.attention_mask)
+                else:
+                    hs = self._encode_graph(tok, B, T) if (side and TEXT_GRAPH[0]) else None
                 if hs is None:
                     hs = self.text_encoder(input_ids=tok.input_ids, attention_mask=tok.attention_mask).last_hidden_state
                 hs32 = hs.reshape(B * T, self.text_dim).float().contiguous()

@@ -486,6 +486,25 @@ int es_layernorm_fwd(const float* x, const float* res, int n, int C, const float
 size_t es_layernorm_bwd_workspace_floats(int n, int C);
 int es_layernorm_bwd(const float* dy, const float* z, int n, int C, const float* w, const float* mean, const float* rstd,
                      float* dz, int accumulate, float* dw, float* db, float* workspace, size_t workspace_floats, void* stream);
+/* ---- frozen RoBERTa text encoder, forward only (embodiedscan_amd/text.py HipTextEncoder; transformers modeling_roberta.py) ----
+ * Every entry point below returns -4 with its outputs untouched when it refuses its arguments.
+ * y (B*T, C) = LayerNorm(word[id] + pos[p] + type0; ln_w, ln_b, eps) with RoBERTa's position rule computed in the kernel:
+ * p = pad_id + (id != pad_id ? #{t' <= t : id[b,t'] != pad_id} : 0).  ids (B,T) int64; an id outside [0, vocab) is taken as
+ * pad_id.  Refused: C > 1024, pad_id outside [0, vocab), pad_id + T >= max_pos.  pos_ids (B*T int32, the positions used) may be NULL. */
+int es_text_embed_ln(const long long* ids, int B, int T, int pad_id, const float* word, const float* pos, const float* type0,
+                     int C, int vocab, int max_pos, const float* ln_w, const float* ln_b, float eps, float* y, int* pos_ids,
+                     void* stream);
+/* y = LayerNorm(x (+ res)) over contiguous (n, C) rows, C <= 1024, no saved statistics; y may alias x or res */
+int es_text_add_ln(const float* x, const float* res, int n, int C, const float* w, const float* b, float eps, float* y,
+                   void* stream);
+/* x[r, c] <- gelu(x[r, c] + bias[c]) for c < C, exact erf form, in place on rows with leading dimension ld >= C */
+int es_bias_gelu(float* x, int ld, int n, int C, const float* bias, void* stream);
+/* masked self-attention, head_dim 64, scale 1/8, on the packed projection qkv (B*T, ld >= 3*H*64): columns [q | k | v], head h at
+ * 64h of each third.  mask_dev (B,T) int32, 0 = key masked (any pattern), NULL = all live; every query row is computed; a sample
+ * without a live key gets O = 0.  O (B*T, ldo >= H*64).  1 <= T <= 512; ld, ldo multiples of 4 floats, qkv 16-byte aligned.
+ * bf16 != 0: bf16 matrix cores (operands and unnormalised probabilities rounded), f32 softmax / accumulation; 0: exact-f32. */
+int es_text_attn_fwd(const float* qkv, int ld, int B, int H, int T, const int* mask_dev, float* O, int ldo, int bf16,
+                     void* stream);
 int es_relu_fwd(float* x, size_t n, void* stream);
 int es_relu_bwd(float* dy, const float* y, size_t n, void* stream);
 /* ContrastiveEmbed (grounding_head.py:62-99, log_scale='auto', bias): logits (B,L,Tout) = <v, text> / sqrt(C) + bias for
