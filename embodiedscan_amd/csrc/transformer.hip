@@ -356,6 +356,232 @@ extern "C" int es_attn_bwd(const float* Q, int ldq, const float* K, int ldk, con
   return 0;
 }
 
+// ------------------------------------------------------------------ attention over ONE prepared key / value set
+// (SparseFeatureFusion3DGrounder.ground: the queries of many prompts over the point tokens of one scene.)  k_attn_fwd stages,
+// converts and transposes every K / V tile once per 64 query rows; here that work is done once per (scene, layer) by
+// es_attn_kv_prepare and the forward kernel copies finished tiles.
+//
+// Operand layout of `kv` (element type: bf16 in bf16 mode, f32 in the parity mode; nt = ceil(Lk / 64) key tiles):
+//   block (h, j) at element ((h * nt + j) * 4096), 4096 = 2 * 64 * 32 elements:
+//     [   0, 2048)  K tile, k-contiguous:  element key * 32 + d        = K[j * 64 + key][h * 32 + d]
+//     [2048, 4096)  V tile, TRANSPOSED:    element 2048 + d * 64 + key = V[j * 64 + key][h * 32 + d]
+//   keys >= Lk are exact zeros (the forward masks their scores; zero keeps 0 * p finite in the PV product).
+// One block is one contiguous run of 16-byte pieces: the forward kernel stages it with two (bf16) / four (f32) 16-byte loads per
+// thread, issued BEFORE the products of the current tile and written to LDS after them (loads in flight under the MFMAs).
+// A workgroup owns 128 query rows of one head (wave w: rows 32 w .. 32 w + 31 as two 16-row tiles; the Q fragments live in
+// registers for the whole key loop), a step is 64 keys: 16 matrix instructions per wave between barriers instead of 4.
+// Rounding points as in k_attn_fwd: f32(q * scale) -> operand type, K / V once (in prepare), online softmax in f32, unnormalised
+// probabilities -> operand type as MFMA operands only.
+#define AK_S 64                         // keys per tile
+#define AK_R 128                        // query rows per workgroup
+#define AK_TILE (2 * AK_S * AT_D)       // elements of one (head, tile) block
+
+template <bool BF> struct AkT;
+template <> struct AkT<true> { typedef unsigned short T; static constexpr int LDK = 40, LDV = 72, EPP = 8; };
+template <> struct AkT<false> { typedef float T; static constexpr int LDK = 36, LDV = 68, EPP = 4; };
+
+// grid (nt, H)
+template <bool BF>
+__global__ __launch_bounds__(256) void k_attn_kv_prepare(const float* __restrict__ K, int ldk, const float* __restrict__ V, int ldv,
+                                                         int Lk, typename AkT<BF>::T* __restrict__ kv) {
+  const int j = blockIdx.x, h = blockIdx.y;
+  typename AkT<BF>::T* dst = kv + ((size_t)h * gridDim.x + j) * AK_TILE;
+  for (int e = threadIdx.x; e < AK_TILE; e += 256) {
+    int key, d;
+    const float* src;
+    int ld;
+    if (e < AK_S * AT_D) { key = e >> 5; d = e & 31; src = K; ld = ldk; }
+    else { d = (e - AK_S * AT_D) >> 6; key = e & 63; src = V; ld = ldv; }
+    const int kg = j * AK_S + key;
+    dst[e] = at_cvt<BF>(kg < Lk ? src[(size_t)kg * ld + h * AT_D + d] : 0.f);
+  }
+}
+
+// the 16-byte pieces of block j that this thread stages: global -> registers ...
+template <bool BF>
+__device__ inline void ak_load(tf32x4_t (&pre)[AK_TILE / AkT<BF>::EPP / 256], const typename AkT<BF>::T* __restrict__ src, int j) {
+  const tf32x4_t* s4 = (const tf32x4_t*)(src + (size_t)j * AK_TILE);
+#pragma unroll
+  for (int u = 0; u < AK_TILE / AkT<BF>::EPP / 256; ++u) pre[u] = s4[u * 256 + threadIdx.x];
+}
+// ... registers -> the padded LDS images Ks [64][LDK], Vt [32][LDV]
+template <bool BF>
+__device__ inline void ak_store(const tf32x4_t (&pre)[AK_TILE / AkT<BF>::EPP / 256], typename AkT<BF>::T* Ks, typename AkT<BF>::T* Vt) {
+  constexpr int LDK = AkT<BF>::LDK, LDV = AkT<BF>::LDV, EPP = AkT<BF>::EPP;
+#pragma unroll
+  for (int u = 0; u < AK_TILE / EPP / 256; ++u) {
+    const int e = (u * 256 + threadIdx.x) * EPP;
+    // (block-uniform per u: pieces u * 256 .. u * 256 + 255 lie on one side of the K / V^T boundary)
+    typename AkT<BF>::T* d;
+    if (u * 256 * EPP < AK_S * AT_D) d = Ks + (e >> 5) * LDK + (e & 31);
+    else d = Vt + ((e - AK_S * AT_D) >> 6) * LDV + (e & 63);
+    *(tf32x4_t*)d = pre[u];                              // 16 bytes: LDK, LDV and the column are multiples of 8 bf16 / 4 f32
+  }
+}
+
+// acc (16x16) += sum_{k<32} A[li][k] B[li][k] with lane (li, kq) supplying k = 8 kq .. 8 kq + 7 of both rows in BOTH modes (the exact-f32
+// instruction sums four lanes' k per step: any assignment of k to (step, lane quarter) is a valid one as long as A and B agree), so a
+// lane's operands are 16 (bf16) / 32 (f32) contiguous bytes of LDS, read as one / two 16-byte loads
+template <bool BF>
+__device__ inline tf32x4_t ak_mma(const typename AkT<BF>::T* arow, const typename AkT<BF>::T* brow, int kq, tf32x4_t acc) {
+  if constexpr (BF) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const tbf16x8_t*)(arow + kq * 8), *(const tbf16x8_t*)(brow + kq * 8), acc, 0, 0, 0);
+  } else {
+    const tf32x4_t a0 = *(const tf32x4_t*)(arow + kq * 8), a1 = *(const tf32x4_t*)(arow + kq * 8 + 4);
+    const tf32x4_t b0 = *(const tf32x4_t*)(brow + kq * 8), b1 = *(const tf32x4_t*)(brow + kq * 8 + 4);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[c], b0[c], acc, 0, 0, 0);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[c], b1[c], acc, 0, 0, 0);
+    return acc;
+  }
+}
+
+// grid (ceil(Lq / 128), H).  Q / O: row i, columns h*32.. of matrices with leading dims ldq / ldo; lse (H, Lq).
+template <bool BF>
+__global__ __launch_bounds__(256) void k_attn_kv_fwd(const float* __restrict__ Q, int ldq, const typename AkT<BF>::T* __restrict__ kv,
+                                                     int Lq, int Lk, float scale, float* __restrict__ O, int ldo,
+                                                     float* __restrict__ lse) {
+  typedef typename AkT<BF>::T T;
+  constexpr int LDK = AkT<BF>::LDK, LDV = AkT<BF>::LDV;
+  __shared__ __attribute__((aligned(16))) T Ks[AK_S * LDK], Vt[AT_D * LDV], Ps[AK_R * LDV];
+  const int h = blockIdx.y, q0 = blockIdx.x * AK_R;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, kq = lane >> 4;
+  const int nt = (Lk + AK_S - 1) / AK_S;
+  const T* src = kv + (size_t)h * nt * AK_TILE;
+  // the A fragments of this wave's two query tiles: lane (li, kq) holds row li, k = 8 kq + j (see ak_mma)
+  typedef short ts16x8_t __attribute__((ext_vector_type(8)));
+  tbf16x8_t qv[2];
+  ts16x8_t qb[2] = {};
+  float qs[2][8];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const int q = q0 + wv * 32 + qt * 16 + li;
+    const float* qr = Q + (size_t)(q < Lq ? q : 0) * ldq + h * AT_D;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x = q < Lq ? qr[kq * 8 + j] * scale : 0.f;
+      if constexpr (BF) qb[qt][j] = (short)f2bf(x);
+      else qs[qt][j] = x;
+    }
+    qv[qt] = __builtin_bit_cast(tbf16x8_t, qb[qt]);
+  }
+  float m[2][4], l[2][4];
+  tf32x4_t o[2][2];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[qt][r] = -INFINITY; l[qt][r] = 0.f; }
+    o[qt][0] = o[qt][1] = (tf32x4_t){0.f, 0.f, 0.f, 0.f};
+  }
+  tf32x4_t pre[AK_TILE / AkT<BF>::EPP / 256];
+  ak_load<BF>(pre, src, 0);
+  for (int j = 0; j < nt; ++j) {
+    const int k0 = j * AK_S;
+    __syncthreads();                                   // the previous step's readers of Ks / Vt / Ps are done
+    ak_store<BF>(pre, Ks, Vt);
+    if (j + 1 < nt) ak_load<BF>(pre, src, j + 1);      // in flight under this step's products
+    __syncthreads();
+    tf32x4_t s[2][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const T* brow = Ks + (t * 16 + li) * LDK;
+      s[0][t] = s[1][t] = (tf32x4_t){0.f, 0.f, 0.f, 0.f};
+      if constexpr (BF) {
+        const tbf16x8_t b = *(const tbf16x8_t*)(brow + kq * 8);
+        s[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qv[0], b, s[0][t], 0, 0, 0);
+        s[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qv[1], b, s[1][t], 0, 0, 0);
+      } else {
+        const tf32x4_t b0 = *(const tf32x4_t*)(brow + kq * 8), b1 = *(const tf32x4_t*)(brow + kq * 8 + 4);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const float b = c < 4 ? b0[c & 3] : b1[c & 3];
+          s[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(qs[0][c], b, s[0][t], 0, 0, 0);
+          s[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(qs[1][c], b, s[1][t], 0, 0, 0);
+        }
+      }
+    }
+    bool ok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) ok[t] = (k0 + t * 16 + li) < Lk;
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float sv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sv[t] = ok[t] ? s[qt][t][r] : -INFINITY;
+        const float mx = group16_max(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])));
+        const float mn = fmaxf(m[qt][r], mx);          // finite: every tile holds at least one key < Lk
+        const float corr = __expf(m[qt][r] - mn);
+        float p[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) p[t] = __expf(sv[t] - mn);
+        l[qt][r] = l[qt][r] * corr + group16_sum((p[0] + p[1]) + (p[2] + p[3]));
+        m[qt][r] = mn;
+        o[qt][0][r] *= corr;
+        o[qt][1][r] *= corr;
+        T* prow = Ps + (wv * 32 + qt * 16 + kq * 4 + r) * LDV;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) prow[t * 16 + li] = at_cvt<BF>(p[t]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+          o[qt][nf] = ak_mma<BF>(Ps + (wv * 32 + qt * 16 + li) * LDV + c * 32, Vt + (nf * 16 + li) * LDV + c * 32, kq, o[qt][nf]);
+  }
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + wv * 32 + qt * 16 + kq * 4 + r;
+      if (q >= Lq) continue;
+      const bool any = l[qt][r] > 0.f;
+      const float inv = any ? 1.f / l[qt][r] : 0.f;
+      float* orow = O + (size_t)q * ldo + h * AT_D;
+      orow[li] = o[qt][0][r] * inv;
+      orow[16 + li] = o[qt][1][r] * inv;
+      if (li == 0) lse[(size_t)h * Lq + q] = any ? m[qt][r] + __logf(l[qt][r]) : -INFINITY;
+    }
+  }
+}
+
+extern "C" size_t es_attn_kv_bytes(int H, int Lk, int bf16) {
+  if (H <= 0 || Lk <= 0) return 0;
+  return (size_t)H * es_cdiv(Lk, AK_S) * AK_TILE * (bf16 ? 2 : 4);
+}
+extern "C" int es_attn_kv_prepare(const float* K, int ldk, const float* V, int ldv, int H, int Lk, int bf16, void* kv, void* stream) {
+  if (H <= 0 || Lk <= 0) return 0;
+  if ((ldk | ldv) & 3) return -3;
+  dim3 grid(es_cdiv(Lk, AK_S), H);
+  if (bf16)
+    hipLaunchKernelGGL(k_attn_kv_prepare<true>, grid, dim3(256), 0, (hipStream_t)stream, K, ldk, V, ldv, Lk, (unsigned short*)kv);
+  else
+    hipLaunchKernelGGL(k_attn_kv_prepare<false>, grid, dim3(256), 0, (hipStream_t)stream, K, ldk, V, ldv, Lk, (float*)kv);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_attn_kv_fwd(const float* Q, int ldq, const void* kv, int H, int Lq, int Lk, float* O, int ldo, float* lse, int bf16,
+                              void* stream) {
+  if (H <= 0 || Lq <= 0 || Lk <= 0) return 0;
+  if ((ldq | ldo) & 3) return -3;
+  dim3 grid(es_cdiv(Lq, AK_R), H);
+  const float scale = 0.17677669529663687f;              // 1 / sqrt(32)
+  if (bf16)
+    hipLaunchKernelGGL(k_attn_kv_fwd<true>, grid, dim3(256), 0, (hipStream_t)stream, Q, ldq, (const unsigned short*)kv, Lq, Lk, scale,
+                       O, ldo, lse);
+  else
+    hipLaunchKernelGGL(k_attn_kv_fwd<false>, grid, dim3(256), 0, (hipStream_t)stream, Q, ldq, (const float*)kv, Lq, Lk, scale, O, ldo,
+                       lse);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ LayerNorm over the channel dim of (n, C) rows
 // z = x (+ res); y = (z - mean) * rstd * w + b.  One wave per row, C <= 512.  z is written out when res != NULL (backward
 // needs the normalised input); mean / rstd saved per row.
@@ -531,6 +757,34 @@ extern "C" int es_relu_bwd(float* dy, const float* y, size_t n, void* stream) {
 // logits[b, i, t] = <v[b,i,:], text[b,t,:]> / sqrt(C) + bias   for t < tlen[b] (and i < vlen[b]); -inf elsewhere, up to Tmax.
 // One wave per visual row; the sample's text block sits in LDS.  rowmax (optional): max_t logits (query selection,
 // sparse_featfusion_grounder.py:370-376).
+// the per-element arithmetic of ContrastiveEmbed, shared by k_contrastive_fwd and k_contrastive_shared_fwd so that the two cannot drift:
+// lane-strided partial sums over C (vv / tt: this lane's channels lane + 64 q of the visual row and of the text token), then the xor
+// butterfly 32, 16, .. 1 over the wave (es_wave_sum, or its 8-row form below), * 1 / sqrt(C), + bias
+__device__ inline float contrastive_partial(const float (&vv)[8], const float (&tt)[8], int C, int lane) {
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) if ((lane + q * 64) < C) s += vv[q] * tt[q];
+  return s;
+}
+__device__ inline float contrastive_logit(const float (&vv)[8], const float (&tt)[8], int C, int lane, float inv, float bv) {
+  return es_wave_sum(contrastive_partial(vv, tt, C, lane)) * inv + bv;
+}
+// es_wave_sum of EIGHT values at once: 10 shuffles instead of 48.  The butterfly steps 32, 16, 8 each halve the number of values a lane
+// carries (a lane keeps the half its lane bit selects and hands the other half to its partner), steps 4, 2, 1 finish the one value left.
+// Every step adds the same two partial sums as es_wave_sum does at that step (a + b = b + a bit for bit), so the result equals
+// es_wave_sum(s[r]) exactly; it arrives in the lanes with ((lane >> 3) & 7) == bit-reversed r, i.e. r = 4 b5 + 2 b4 + b3 of the lane.
+__device__ inline float wave_sum8(const float (&s)[8], int lane) {
+  float a[4], b[2], c;
+  const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = (h5 ? s[i + 4] : s[i]) + __shfl_xor(h5 ? s[i] : s[i + 4], 32, 64);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) b[i] = (h4 ? a[i + 2] : a[i]) + __shfl_xor(h4 ? a[i] : a[i + 2], 16, 64);
+  c = (h3 ? b[1] : b[0]) + __shfl_xor(h3 ? b[0] : b[1], 8, 64);
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  return c;
+}
 __global__ __launch_bounds__(256) void k_contrastive_fwd(const float* __restrict__ v, int L, const float* __restrict__ text, int T,
                                                          int C, const int* __restrict__ tlen, const int* __restrict__ vlen,
                                                          const float* __restrict__ bias, float* __restrict__ logits, int Tout,
@@ -552,10 +806,10 @@ __global__ __launch_bounds__(256) void k_contrastive_fwd(const float* __restrict
     for (int t = 0; t < Tout; ++t) {
       float out = -INFINITY;
       if (t < tl && i < vl) {
-        float s = 0.f;
+        float tt[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) if ((lane + q * 64) < C) s += vv[q] * ts[t * C + lane + q * 64];
-        out = es_wave_sum(s) * inv + bv;
+        for (int q = 0; q < 8; ++q) tt[q] = (lane + q * 64) < C ? ts[t * C + lane + q * 64] : 0.f;
+        out = contrastive_logit(vv, tt, C, lane, inv, bv);
       }
       best = fmaxf(best, out);
       if (logits && lane == 0) logits[((size_t)b * L + i) * Tout + t] = out;
@@ -572,6 +826,66 @@ extern "C" int es_contrastive_fwd(const float* v, int B, int L, const float* tex
   if (sh > 64 * 1024) ES_TRY(hipFuncSetAttribute((const void*)k_contrastive_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
   hipLaunchKernelGGL(k_contrastive_fwd, dim3(min(es_cdiv(L, 4), 256), B), dim3(256), sh, (hipStream_t)stream, v, L, text, T, C,
                      tlen_dev, vlen_dev, bias_dev, logits, Tout, rowmax);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+// ContrastiveEmbed of ONE scene's L rows against P prompts' text blocks (SparseFeatureFusion3DGrounder.ground): logits (P, L, Tout),
+// rowmax (P, L), bit-identical to es_contrastive_fwd on P copies of the rows (same partial sums, same butterfly: see wave_sum8).  A wave
+// holds CS_R = 8 visual rows in registers (a workgroup: 32 consecutive rows, loaded ONCE) while the prompts' text blocks stream through
+// LDS; a staged text channel is read from LDS once for the wave's 8 rows and the 8 wave sums of a token are one 10-shuffle reduction --
+// the composition it replaces pays 8 LDS reads and 6 shuffles per logit, which is where its time goes.  After the reduction the lanes
+// with lane >> 3 == (b5 b4 b3) hold row r = 4 b5 + 2 b4 + b3 of the wave; the lane with (lane & 7) == 0 of each group writes.
+// grid (ceil(L / 32), ny): workgroup (x, y) takes the prompts y, y + ny, ... (ny > 1 only when the rows alone would not fill the chip).
+// tlen[p] <= 0: a row of -inf.
+#define CS_R 8
+__global__ __launch_bounds__(256) void k_contrastive_shared_fwd(const float* __restrict__ v, int L, const float* __restrict__ text, int P,
+                                                                int T, int C, const int* __restrict__ tlen,
+                                                                const float* __restrict__ bias, float* __restrict__ logits, int Tout,
+                                                                float* __restrict__ rowmax) {
+  extern __shared__ float ts[];                         // T * C
+  const int lane = threadIdx.x & 63;
+  const float inv = 1.f / sqrtf((float)C), bv = bias ? bias[0] : 0.f;
+  const int i0 = blockIdx.x * (4 * CS_R) + (threadIdx.x >> 6) * CS_R;
+  float vv[CS_R][8];
+#pragma unroll
+  for (int r = 0; r < CS_R; ++r) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) vv[r][q] = (i0 + r < L && (lane + q * 64) < C) ? v[(size_t)(i0 + r) * C + lane + q * 64] : 0.f;
+  }
+  const int mine = i0 + ((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1);      // the row this lane ends up holding
+  const bool writer = (lane & 7) == 0 && mine < L;
+  for (int p = blockIdx.y; p < P; p += gridDim.y) {
+    const int tl = min(min(tlen[p], T), Tout);          // tokens beyond the Tout written columns are not staged (nor in rowmax)
+    __syncthreads();                                    // the previous prompt's readers are done
+    for (int e = threadIdx.x; e < tl * C; e += 256) ts[e] = text[(size_t)p * T * C + e];
+    __syncthreads();
+    float best = -INFINITY;
+    for (int t = 0; t < Tout; ++t) {
+      float out = -INFINITY;
+      if (t < tl) {                                     // (workgroup-uniform)
+        float tt[8], s[CS_R];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tt[q] = (lane + q * 64) < C ? ts[t * C + lane + q * 64] : 0.f;
+#pragma unroll
+        for (int r = 0; r < CS_R; ++r) s[r] = contrastive_partial(vv[r], tt, C, lane);
+        out = wave_sum8(s, lane) * inv + bv;
+      }
+      best = fmaxf(best, out);
+      if (logits && writer) logits[((size_t)p * L + mine) * Tout + t] = out;
+    }
+    if (rowmax && writer) rowmax[(size_t)p * L + mine] = best;
+  }
+}
+extern "C" int es_contrastive_shared_fwd(const float* v, int L, const float* text, int P, int T, int C, const int* tlen_dev,
+                                         const float* bias_dev, float* logits, int Tout, float* rowmax, void* stream) {
+  if (P <= 0 || L <= 0) return 0;
+  if (C > 512 || (size_t)T * C * 4 > 160 * 1024 - 1024) return -4;
+  size_t sh = (size_t)T * C * sizeof(float);
+  if (sh > 64 * 1024) ES_TRY(hipFuncSetAttribute((const void*)k_contrastive_shared_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+  const int nx = es_cdiv(L, 4 * CS_R);
+  const int ny = min(P, max(1, es_cdiv(512, nx)));
+  hipLaunchKernelGGL(k_contrastive_shared_fwd, dim3(nx, ny), dim3(256), sh, (hipStream_t)stream, v, L, text, P, T, C, tlen_dev, bias_dev,
+                     logits, Tout, rowmax);
   ES_CHECK_LAUNCH();
   return 0;
 }

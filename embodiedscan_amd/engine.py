@@ -1315,3 +1315,47 @@ def attention(q, k, v, B, H, Lq, Lk, klen=None):
             rec.update(delta=delta.clone(), dq=q.g.clone(), dk=k.g.clone(), dv=v.g.clone())
     TAPE.add(bwd)
     return o
+
+
+# ---- one scene, many prompts (SparseFeatureFusion3DGrounder.ground): forward only, nothing on the tape
+class PreparedKV:
+    """the projected keys / values of one cross-attention layer in the operand image es_attn_kv_fwd consumes (csrc/transformer.hip),
+    built once per scene; k / v: the f32 projections, kept only when DEBUG_FWD was set at build time (the forward record needs them)"""
+    __slots__ = ('kv', 'H', 'Lk', 'bf', 'k', 'v')
+
+
+def attention_kv_prepare(k, v, H, Lk):
+    """k / v: Vars (Lk, H*32), the projected point tokens of one scene -> PreparedKV in the precision of the current mode"""
+    bf = 1 if PRECISION[0] == 'bf16' else 0
+    pk = PreparedKV()
+    pk.H, pk.Lk, pk.bf = H, Lk, bf
+    pk.kv = torch.empty(int(hip.raw('es_attn_kv_bytes')(H, Lk, bf)), dtype=torch.uint8, device=k.d.device)
+    call('es_attn_kv_prepare', P(k.d), _ld(k.d), P(v.d), _ld(v.d), H, Lk, bf, P(pk.kv), _stream())
+    pk.k, pk.v = (k.d, v.d) if DEBUG_FWD is not None else (None, None)
+    return pk
+
+
+def attention_kv(q, pk, Lq):
+    """softmax(q k^T / sqrt(32)) v per head of Lq query rows (any number of prompts' queries) over the ONE prepared key / value set"""
+    H, Lk = pk.H, pk.Lk
+    o = Var(empty((Lq, H * 32), q.d), rg=False)
+    lse = empty((H * Lq,), q.d)
+    call('es_attn_kv_fwd', P(q.d), _ld(q.d), P(pk.kv), H, Lq, Lk, P(o.d), H * 32, P(lse), pk.bf, _stream())
+    if DEBUG_FWD is not None:
+        if pk.k is None:
+            raise RuntimeError('DEBUG_FWD: this scene encoding was built without it (the record needs the f32 projections): rebuild it')
+        fwd_record('attention', 'es_attn_kv_fwd', q=q.d, k=pk.k, v=pk.v, B=1, H=H, Lq=Lq, Lk=Lk, klen=None, bf=pk.bf, o=o.d, lse=lse)
+    return o
+
+
+def contrastive_shared(v, L, text, n_prompts, T, tlen, bias, want_logits=False, want_max=True):
+    """ContrastiveEmbed of one scene's rows v (L, C) against n_prompts text blocks (n_prompts*T, C) -> (logits (n_prompts*L, T) or None,
+    rowmax (n_prompts*L,) or None); raw tensors"""
+    C = v.shape[1]
+    logits = torch.empty((n_prompts * L, T), dtype=torch.float32, device=v.device) if want_logits else None
+    rowmax = torch.empty(n_prompts * L, dtype=torch.float32, device=v.device) if want_max else None
+    call('es_contrastive_shared_fwd', P(v), L, P(text), n_prompts, T, C, P(tlen), P(bias), P(logits), T, P(rowmax), _stream())
+    if DEBUG_FWD is not None:                    # the replicated reading: what es_contrastive_fwd computes on n_prompts copies of the rows
+        fwd_record('contrastive', 'es_contrastive_shared_fwd', v=v.repeat(n_prompts, 1), text=text, B=n_prompts, L=L, T=T, tlen=tlen,
+                   vlen=None, bias=bias, logits=logits, rowmax=rowmax)
+    return logits, rowmax

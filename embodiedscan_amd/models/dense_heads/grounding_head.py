@@ -120,6 +120,11 @@ class GroundingHead:
             E.TAPE.add(bwd)
         return logits, rowmax
 
+    def cls_branch_shared(self, visual, text, P_, T, tlen, want_logits=False, want_max=True):
+        """cls_branch of ONE scene's rows `visual` (raw (L, E)) against P_ prompts' text Var (P_*T, E), forward only ->
+        (logits (P_*L, T) or None, rowmax (P_*L,) or None), bit-identical to cls_branch on P_ copies of the rows"""
+        return E.contrastive_shared(visual, visual.shape[0], text.d, P_, T, tlen, self.cls_bias.d, want_logits, want_max)
+
     # ------------------------------------------------------------------ ground truth upload
     @staticmethod
     def pack_gt(batch_gt_instances_3d, T, dev):

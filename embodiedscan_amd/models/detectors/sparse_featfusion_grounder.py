@@ -18,6 +18,28 @@ TEXT_GRAPH = [os.environ.get('ES_TEXT_GRAPH', '1') != '0']     # ... as a captur
 TEXT_ASYNC = [os.environ.get('ES_TEXT_ASYNC', '1') != '0']     # round 6: the frozen text encoder on its own stream, queued before the backbones
 
 
+class SceneEncoding:
+    """One scan encoded once (encode_scene / scene_from_tokens): everything of the grounder that does not depend on the prompt.
+    feats (L, E) / points (L, 3): the MinkNeck tokens; keys: the decoder's prepared key side, one engine.PreparedKV per layer;
+    precision / weight_version: engine.PRECISION[0] / engine.WEIGHT_VERSION[0] when it was built -- ground() refuses the encoding once
+    either has moved (the cached projections are stale then)."""
+    __slots__ = ('feats', 'points', 'L', 'keys', 'precision', 'weight_version')
+
+    def __init__(self, feats, points, keys, precision, weight_version):
+        self.feats, self.points, self.L, self.keys = feats, points, int(feats.shape[0]), keys
+        self.precision, self.weight_version = precision, weight_version
+
+
+class _Prompt:
+    """what start_text / finish_text / bbox_head.predict read of a data sample"""
+
+    def __init__(self, text, tokens_positive):
+        import types
+        # (no spans given: one target on the first character -- the positive maps do not enter the prediction)
+        self.text, self.tokens_positive = text, tokens_positive if tokens_positive is not None else [[(0, 1)]]
+        self.gt_instances_3d = types.SimpleNamespace()
+
+
 @MODELS.register_module()
 class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
     _version = 2
@@ -278,3 +300,97 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         for ds, r in zip(batch_data_samples, results):
             ds.pred_instances_3d = r
         return batch_data_samples
+
+    # ------------------------------------------------------------------ one scene, many prompts
+    def _eval_guard(self):
+        """the eval / tape-off state of predict() as a context manager"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def guard():
+            was, prev = self.training, E.TAPE.enabled
+            hip.refresh_stream()
+            self.train(False)
+            E.TAPE.enabled = False
+            try:
+                self._bind()
+                yield
+            finally:
+                E.TAPE.enabled = prev
+                self.train(was)
+        return guard()
+
+    def scene_from_tokens(self, feats, points):
+        """SceneEncoding of an (L, E) / (L, 3) pair of device tensors (MinkNeck tokens of one scan, e.g. from a cache file)"""
+        feats = feats.to(device=self.device, dtype=torch.float32).contiguous()
+        points = points.to(device=self.device, dtype=torch.float32).contiguous()
+        if feats.dim() != 2 or feats.shape[1] != self.embed_dims or tuple(points.shape) != (feats.shape[0], 3):
+            raise ValueError(f'expected ({{L}}, {self.embed_dims}) features and ({{L}}, 3) points, got {tuple(feats.shape)} / {tuple(points.shape)}')
+        with self._eval_guard():
+            keys = self.decoder.prepare_keys(E.Var(feats, rg=False), points) if feats.shape[0] else []
+        return SceneEncoding(feats, points, keys, E.PRECISION[0], E.WEIGHT_VERSION[0])
+
+    def encode_scene(self, batch_inputs_dict, batch_data_samples):
+        """one SceneEncoding per sample of the batch (the samples' text is ignored): 2-D / 3-D backbones, fusion and MinkNeck run
+        HERE, once per scan; ground() then answers any number of prompts on it"""
+        with self._eval_guard():
+            self.extract_feat(batch_inputs_dict, batch_data_samples)
+            nk = self.neck_3d.last
+            Lmax = nk['Lmax']
+            cut = [(nk['feats'].d[b * Lmax:b * Lmax + n].clone(), nk['points'][b * Lmax:b * Lmax + n].clone()) for b, n in enumerate(nk['lens'])]
+        return [self.scene_from_tokens(f, p) for f, p in cut]
+
+    def ground(self, scene, prompts, tokens_positive=None, max_prompts=64):
+        """InstanceData(bboxes_3d, scores_3d, target_scores_3d) per prompt -- what predict() attaches to a (scene, prompt) sample -- for
+        any number of prompts on one encoded scene, Q = min(num_queries, L) rows each.  prompts: strings or objects with .text (and
+        optionally .tokens_positive); processed in chunks of at most max_prompts."""
+        from ...structures import EulerDepthInstance3DBoxes, InstanceData
+        if scene.precision != E.PRECISION[0] or scene.weight_version != E.WEIGHT_VERSION[0]:
+            raise ValueError(f'stale scene encoding: built under precision {scene.precision!r} / weight version {scene.weight_version}, now '
+                             f'{E.PRECISION[0]!r} / {E.WEIGHT_VERSION[0]}: encode the scene again')
+        if scene.feats.device != self.device:
+            raise ValueError(f'the scene encoding is on {scene.feats.device}, the grounder on {self.device}')
+        if max_prompts < 1:
+            raise ValueError('max_prompts must be positive')
+        samples = []
+        for i, pr in enumerate(prompts):
+            tp = tokens_positive[i] if tokens_positive is not None else getattr(pr, 'tokens_positive', None)
+            samples.append(_Prompt(pr if isinstance(pr, str) else pr.text, tp))
+        if not samples:
+            return []
+        dev, L = self.device, scene.L
+        if L == 0:
+            z = torch.zeros(0, dtype=torch.float32, device=dev)
+            return [InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(torch.zeros((0, 9), dtype=torch.float32, device=dev)), scores_3d=z,
+                                 target_scores_3d=z) for _ in samples]
+        Q = min(self.num_queries, L)
+        force = getattr(self, 'force_queries', None)
+        results, free, texts, sel = [], [], [], []
+        s = hip.stream()
+        with self._eval_guard():
+            for c0 in range(0, len(samples), max_prompts):
+                chunk = samples[c0:c0 + max_prompts]
+                n = len(chunk)
+                text, mask, tlen, T = self.encode_text(chunk)
+                texts.append(self.last_text)
+                # query selection per prompt: the scene's rows scored against every prompt's tokens, top-k of the (n, L) row maxima
+                _, rowmax = self.bbox_head.cls_branch_shared(scene.feats, text, n, T, tlen)
+                klen = torch.full((n,), L, dtype=torch.int32, device=dev)
+                idx = torch.empty((n, Q), dtype=torch.int32, device=dev)
+                call('es_topk_sorted', P(rowmax), n, L, P(klen), Q, P(idx), s)
+                if force is not None:                    # test hook (teacher forcing), shape (P, Q): see forward_transformer
+                    free.append(idx)
+                    idx = force[c0:c0 + n].to(device=dev, dtype=torch.int32).reshape(n, Q).contiguous()
+                sel.append(idx)
+                gidx = idx.reshape(-1)                   # rows of the ONE scene: no per-sample offset
+                query = E.gather_rows(E.Var(scene.feats, rg=False), gidx)
+                qcoords = torch.empty((n * Q, 3), dtype=torch.float32, device=dev)
+                call('es_row_move', P(qcoords), 3, P(scene.points), 3, P(gidx), n * Q, 3, 0, s)
+                pred0 = self.bbox_head.decode(qcoords, self.bbox_head.reg_branch(E.Var(query.d, rg=False))).d
+                hidden, boxes = self.decoder.forward_shared(query, scene.keys, qcoords, pred0, text, n, Q, T, tlen, self.bbox_head)
+                results += self.bbox_head.predict(hidden, boxes, text, mask, chunk, tlen=tlen)
+        self.last_text_chunks = texts                    # last_text of every chunk (the padded token count differs between chunks)
+        self.last_queries = dict(idx=torch.cat(sel), Q=Q)
+        if force is not None:
+            self.free_queries = torch.cat(free)
+        return results

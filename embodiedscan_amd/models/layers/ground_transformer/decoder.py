@@ -78,6 +78,15 @@ class _MHA:
         o = E.attention(q, k, v, B, self.H, Lq, Lk, klen)
         return self.out(o), query        # (attention branch, identity): the caller fuses the add into the LayerNorm
 
+    def project_kv(self, k_in, v_in):
+        """the key side alone: (k_in Wk + bk, v_in Wv + bv)"""
+        return E.linear(k_in, self.wk, self.bias[1], need_dx=False), E.linear(v_in, self.wv, self.bias[2], need_dx=False)
+
+    def on_prepared(self, query, q_in, prepared, Lq):
+        """__call__ with the key side taken from an engine.PreparedKV (one scene's point tokens, any number of prompts' queries)"""
+        q = E.linear(q_in, self.wq, self.bias[0])
+        return self.out(E.attention_kv(q, prepared, Lq)), query
+
 
 class DecoderLayer:
     def __init__(self, arena, p, H):
@@ -88,8 +97,9 @@ class DecoderLayer:
         self.ffn1 = _Lin(arena, p + 'ffn.layers.1.weight', p + 'ffn.layers.1.bias')
         self.norms = [_LN(arena, p + f'norms.{k}') for k in range(4)]
 
-    def __call__(self, query, query_pos, key, key_with_pos, text, B, Q, Lk, T, klen, tlen):
-        """decoder.py:103-179"""
+    def __call__(self, query, query_pos, key, key_with_pos, text, B, Q, Lk, T, klen, tlen, prepared=None):
+        """decoder.py:103-179.  prepared (engine.PreparedKV): the point cross-attention reads this one scene's prepared key side for
+        all B * Q query rows instead of projecting key / key_with_pos (forward_shared)"""
         qp = E.add(query, query_pos)
         a, idt = self.self_attn(query, qp, qp, query, B, Q, Q, None)
         query = self.norms[0](a, res=idt)
@@ -97,7 +107,10 @@ class DecoderLayer:
         a, idt = self.cross_attn_text(query, qp, text, text, B, Q, T, tlen)
         query = self.norms[1](a, res=idt)
         qp = E.add(query, query_pos)
-        a, idt = self.cross_attn(query, qp, key_with_pos, key, B, Q, Lk, klen)
+        if prepared is None:
+            a, idt = self.cross_attn(query, qp, key_with_pos, key, B, Q, Lk, klen)
+        else:
+            a, idt = self.cross_attn.on_prepared(query, qp, prepared, B * Q)
         query = self.norms[2](a, res=idt)
         h = E.relu_(self.ffn0(query))
         return self.norms[3](self.ffn1(h), res=query)
@@ -140,3 +153,28 @@ class SparseFeatureFusionTransformerDecoder:
         return inter, boxes
 
     __call__ = forward
+
+    def prepare_keys(self, key, key_coords):
+        """the prompt-independent key side of the point cross-attention for ONE scene, eval mode, tape off: key Var (L, E), key_coords
+        (L, 3) -> [engine.PreparedKV per layer] (cross_posembed once, then per layer K = (key + pos) Wk + bk, V = key Wv + bv and
+        es_attn_kv_prepare)"""
+        L = key.d.shape[0]
+        key_with_pos = E.add(key, self.cross_posembed(key_coords, False))
+        out = []
+        for layer in self.layers:
+            k, v = layer.cross_attn.project_kv(key_with_pos, key)
+            out.append(E.attention_kv_prepare(k, v, self.num_heads, L))
+        return out
+
+    def forward_shared(self, query, prepared, query_coords, pred_bboxes, text, P, Q, T, tlen, bbox_head):
+        """forward() in eval mode for P prompts on one scene: query Var (P*Q, E), text Var (P*T, E); self-attention and the text
+        cross-attention run per prompt (B = P), the point cross-attention on the prepared key side of prepare_keys()"""
+        inter, boxes = [], []
+        for layer, pk in zip(self.layers, prepared):
+            query_pos = self.self_posembed(pred_bboxes, False)
+            query = layer(query, query_pos, None, None, text, P, Q, pk.Lk, T, None, tlen, prepared=pk)
+            new_boxes = bbox_head.decode(query_coords, bbox_head.reg_branch(query))
+            pred_bboxes = new_boxes.d
+            inter.append(self.norm(query))
+            boxes.append(new_boxes)
+        return inter, boxes

@@ -472,6 +472,17 @@ int es_occ_loss(const float* logits, int ld, const int* gt, int n, int C, float 
  * with f32 softmax / accumulation; 0: exact-f32 matrix cores.  All leading dims multiples of 4 floats. */
 int es_attn_fwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int Lq, int Lk,
                 const int* klen_dev, float* O, int ldo, float* lse, int bf16, void* stream);
+/* Attention of many query rows over ONE key / value set that is prepared once (SparseFeatureFusion3DGrounder.ground: the queries
+ * of P prompts over the point tokens of one scene).  es_attn_kv_prepare puts the projected K / V (Lk rows, head h in columns
+ * [32h, 32h+32), leading dims multiples of 4 floats) into the operand image the forward kernel consumes -- per (head, 64-key
+ * tile) a k-contiguous K tile followed by the transposed V tile, bf16 (bf16 != 0) or f32, keys >= Lk zero; layout documented at
+ * the kernel, csrc/transformer.hip -- in a device buffer of es_attn_kv_bytes(H, Lk, bf16) bytes (16-byte aligned).
+ * es_attn_kv_fwd: O (Lq, H*32) = softmax(q k^T / sqrt(32)) v per head over all Lk keys, lse (H, Lq); same rounding points as
+ * es_attn_fwd with B = 1; `bf16` must be the value the image was prepared with. */
+size_t es_attn_kv_bytes(int H, int Lk, int bf16);
+int es_attn_kv_prepare(const float* K, int ldk, const float* V, int ldv, int H, int Lk, int bf16, void* kv, void* stream);
+int es_attn_kv_fwd(const float* Q, int ldq, const void* kv, int H, int Lq, int Lk, float* O, int ldo, float* lse, int bf16,
+                   void* stream);
 /* gradients of the same (recomputing the probabilities from lse); delta_scratch: B*H*Lq floats */
 int es_attn_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
                 const float* dO, int ldd, const float* lse, int B, int H, int Lq, int Lk, const int* klen_dev,
@@ -511,6 +522,10 @@ int es_relu_bwd(float* dy, const float* y, size_t n, void* stream);
  * t < tlen[b] (and rows < vlen[b]), -inf elsewhere; rowmax (B,L) = max over tokens (either output may be NULL) */
 int es_contrastive_fwd(const float* v, int B, int L, const float* text, int T, int C, const int* tlen_dev, const int* vlen_dev,
                        const float* bias_dev, float* logits, int Tout, float* rowmax, void* stream);
+/* the same for ONE scene's L rows v (L, C) against P prompts' text blocks (P, T, C): logits (P, L, Tout) (may be NULL), rowmax
+ * (P, L), bit-identical to es_contrastive_fwd on P copies of v (no vlen: every row is live); tlen[p] <= 0 gives a row of -inf */
+int es_contrastive_shared_fwd(const float* v, int L, const float* text, int P, int T, int C, const int* tlen_dev,
+                              const float* bias_dev, float* logits, int Tout, float* rowmax, void* stream);
 size_t es_contrastive_bwd_workspace_floats(int B, int T);
 /* dtext: one workgroup per (sample, token) adds the rows in ascending order; dbias: per-workgroup partials in `workspace` (same
  * ticket convention as es_layernorm_bwd) summed in index order by the last workgroup.  Deterministic, no float atomics. */
