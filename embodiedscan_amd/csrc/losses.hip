@@ -18,7 +18,9 @@
 __global__ __launch_bounds__(256) void k_focal(const float* __restrict__ logits, int ldl,
                                                const int* __restrict__ labels, int N, int C, float gamma,
                                                float alpha, const float* __restrict__ avg_factor, float grad_scale,
-                                               float* __restrict__ grad, int ldg, double* __restrict__ partial) {
+                                               float* __restrict__ grad, int ldg, double* __restrict__ partial, int lead, int tail) {
+  // lead, tail: floats before / after the class block of each gradient row that the row's wave also clears (es_focal_loss_clear; 0, 0:
+  // es_focal_loss)
   __shared__ double red[4];
   const float inv = grad_scale / (avg_factor[0] + 1.1920929e-07f);
   const bool g2 = gamma == 2.f;
@@ -48,6 +50,10 @@ __global__ __launch_bounds__(256) void k_focal(const float* __restrict__ logits,
       acc += l;
       if (grow) grow[c] = g * inv;
     }
+    if (grow) {
+      for (int c = lane; c < lead; c += 64) grow[c - lead] = 0.f;
+      for (int c = lane; c < tail; c += 64) grow[C + c] = 0.f;
+    }
     s += (double)acc;
   }
   s = es_wave_sum_d(s);
@@ -73,12 +79,22 @@ __global__ void k_sum_partials(const double* __restrict__ partial, int n, const 
 extern "C" int es_focal_loss(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
                              const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial,
                              float* loss_out, void* stream) {
+  return es_focal_loss_clear(logits, ldl, labels, N, C, gamma, alpha, avg_factor_dev, grad_scale, grad, ldg, partial, loss_out, 0, 0,
+                             stream);
+}
+// es_focal_loss that also OWNS the rest of its N gradient rows: the `lead` floats before and the `tail` floats after the class block that
+// `grad` points at are set to +0 by the row's wave (the head's (N, 320) gradient matrix -- 13 regression / centerness columns, 284
+// classes, 23 padding columns -- then needs no zero fill: one pass over it less).  Loss value and class gradients are es_focal_loss's.
+extern "C" int es_focal_loss_clear(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
+                                   const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial,
+                                   float* loss_out, int lead, int tail, void* stream) {
+  if (lead < 0 || tail < 0 || ((lead || tail) && (!grad || lead + C + tail > ldg))) return -3;
   hipStream_t st = (hipStream_t)stream;
   int g = es_cdiv(N, 4);
   if (g > FOCAL_BLOCKS) g = FOCAL_BLOCKS;
   if (g < 1) g = 1;
   hipLaunchKernelGGL(k_focal, dim3(g), dim3(256), 0, st, logits, ldl, labels, N, C, gamma, alpha, avg_factor_dev,
-                     grad_scale, grad, ldg, partial);
+                     grad_scale, grad, ldg, partial, lead, tail);
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, partial, g, avg_factor_dev, loss_out);
   ES_CHECK_LAUNCH();
   return 0;

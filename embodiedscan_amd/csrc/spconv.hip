@@ -2423,7 +2423,9 @@ __global__ __launch_bounds__(256) void k_spconv_wgrad_bf16_big(const void* __res
                                                                const int* __restrict__ nbr, int n_out, int n_in, int K,
                                                                int Cin, int Cout, int rows_per_split,
                                                                int n_slices, float* __restrict__ dW, float* __restrict__ ws,
-                                                               int accumulate) {
+                                                               int accumulate, int tap_cols) {
+  // tap_cols: tap k reads its dY rows from column k * tap_cols on (the generative transposed convolution's (n, 8 Cout) gradient rows,
+  // es_gen_transpose_wgrad_bf16); 0 for every other launch
   __shared__ __attribute__((aligned(16))) unsigned short As[128 * GLD];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[128 * GLD];
   __shared__ int s_qj[QCAP], s_qi[QCAP], s_wc[4];
@@ -2432,7 +2434,7 @@ __global__ __launch_bounds__(256) void k_spconv_wgrad_bf16_big(const void* __res
   int bx, by, bz;
   if (!xcd_slice_order(n_slices, bx, by, bz)) return;
   const int k = bx / nCt, c0 = (bx % nCt) * 128;
-  const int n0 = by * 128;
+  const int n0 = by * 128, y0 = n0 + k * tap_cols;
   const int rbeg = bz * rows_per_split;
   const int rend = min(n_out, rbeg + rows_per_split);
   // staging: thread = (pair-of-pairs rp 0..15, channel group cg 0..15); it converts channels cg*8 .. cg*8+7 of ring
@@ -2465,9 +2467,9 @@ __global__ __launch_bounds__(256) void k_spconv_wgrad_bf16_big(const void* __res
         xa[h][0] = px[0]; xa[h][XH ? 0 : 1] = px[1];
       }
       if (YH) {
-        hb[h] = *(const uint4*)((const unsigned short*)dYv + j * ldy + n0 + c8);
+        hb[h] = *(const uint4*)((const unsigned short*)dYv + j * ldy + y0 + c8);
       } else {
-        const float4* py = (const float4*)((const float*)dYv + j * ldy + n0 + c8);
+        const float4* py = (const float4*)((const float*)dYv + j * ldy + y0 + c8);
         xb[h][0] = py[0]; xb[h][YH ? 0 : 1] = py[1];
       }
     }
@@ -2783,11 +2785,14 @@ __global__ __launch_bounds__(512) void k_spconv_wgrad_bf16_huge(const unsigned s
 // workspace block (added in slice order by the reduction launch every weight-gradient launch ends with).
 __global__ __launch_bounds__(256) void k_lin_wgrad_small(const float* __restrict__ X, int ldx, const float* __restrict__ dY, int ldy, int n,
                                                          int Cin, int Cout, int rows_per_split, float* __restrict__ dW,
-                                                         float* __restrict__ ws, int accumulate) {
+                                                         float* __restrict__ ws, int accumulate, int K, int tap_cols) {
+  // K, tap_cols: 1, 0 -- or the 8 taps of es_gen_transpose_wgrad_bf16 as a grid dimension: tap k = blockIdx.x / (Cin / 64) reads its
+  // dY rows from column k * tap_cols on and owns dW[k]
   __shared__ __attribute__((aligned(16))) unsigned short Xt[64 * LS_LD];
   __shared__ __attribute__((aligned(16))) unsigned short Yt[64 * LS_LD];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 15, kq = lane >> 4;
-  const int c0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
+  const int nCt = Cin / 64, k = blockIdx.x / nCt;
+  const int c0 = (blockIdx.x % nCt) * 64, n0 = blockIdx.y * 64, y0 = n0 + k * tap_cols;
   const int rbeg = blockIdx.z * rows_per_split, rend = min(n, rbeg + rows_per_split);
   f32x4 acc[4];
 #pragma unroll
@@ -2798,7 +2803,7 @@ __global__ __launch_bounds__(256) void k_lin_wgrad_small(const float* __restrict
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       rx[i] = row < rend ? *(const float4*)(X + (size_t)row * ldx + c0 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-      ry[i] = row < rend ? *(const float4*)(dY + (size_t)row * ldy + n0 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      ry[i] = row < rend ? *(const float4*)(dY + (size_t)row * ldy + y0 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -2829,7 +2834,8 @@ __global__ __launch_bounds__(256) void k_lin_wgrad_small(const float* __restrict
   for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      wgrad_emit(dW, ws, blockIdx.z, (size_t)Cin * Cout, (size_t)(c0 + wv * 16 + kq * 4 + r) * Cout + n0 + nf * 16 + li, acc[nf][r], accumulate);
+      wgrad_emit(dW, ws, blockIdx.z, (size_t)K * Cin * Cout, ((size_t)k * Cin + c0 + wv * 16 + kq * 4 + r) * Cout + n0 + nf * 16 + li, acc[nf][r],
+                 accumulate);
 }
 static bool lin_wgrad_small_ok(int XH, int YH, const void* X, int ldx, const void* dY, int ldy, int n_out, int n_in, int K, int Cin, int Cout) {
   return ES_OPT_LIN_SMALL && K == 1 && !XH && !YH && n_out == n_in && n_out <= 8192 && (Cin % 64 == 0) && (Cout % 64 == 0) &&
@@ -2895,7 +2901,7 @@ static int wgrad_bf16_launch(const void* X, int ldx, const void* dY, int ldy, co
   hipStream_t st = (hipStream_t)stream;
   if (p.kind == 5 && nbr == nullptr) {
     hipLaunchKernelGGL(k_lin_wgrad_small, dim3(Cin / 64, Cout / 64, p.splits), dim3(256), 0, st, (const float*)X, ldx, (const float*)dY, ldy,
-                       n_out, Cin, Cout, p.rows_per_split, dW, wsk, accumulate);
+                       n_out, Cin, Cout, p.rows_per_split, dW, wsk, accumulate, 1, 0);
   } else if (p.kind == 3) {
     dim3 grid(K * (Cin / 256), Cout / 256, gz);
     hipLaunchKernelGGL(k_spconv_wgrad_bf16_huge, grid, dim3(512), 0, st, (const unsigned short*)X, ldx,
@@ -2911,7 +2917,7 @@ static int wgrad_bf16_launch(const void* X, int ldx, const void* dY, int ldy, co
   } else if (p.kind == 2) {
     dim3 grid(K * (Cin / 128), Cout / 128, gz);
     hipLaunchKernelGGL((k_spconv_wgrad_bf16_big<XH, YH>), grid, dim3(256), 0, st, X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin,
-                       Cout, p.rows_per_split, p.splits, dW, wsk, accumulate);
+                       Cout, p.rows_per_split, p.splits, dW, wsk, accumulate, 0);
   } else {
     dim3 grid(K * es_cdiv(Cin, WM), es_cdiv(Cout, WN), gz);
     hipLaunchKernelGGL((k_spconv_wgrad_bf16<XH, YH>), grid, dim3(256), 0, st, X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin,
@@ -2934,6 +2940,43 @@ extern "C" int es_spconv_wgrad_bf16_src(const void* X, int x_half, int ldx, cons
   if (x_half) return wgrad_bf16_launch<1, 0>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
   if (dy_half) return wgrad_bf16_launch<0, 1>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
   return wgrad_bf16_launch<0, 0>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
+}
+
+// Weight gradient of the generative transposed convolution (k = 2, s = 2: y[8 i + k] = x[i] @ w[k]), all eight taps in ONE launch:
+// dW[k] (+)= X^T dY[:, k Cout .. (k + 1) Cout) on the (n, 8 Cout) view of the output gradient.  The tap is a grid dimension of the
+// kernel a single tap's es_spconv_wgrad_bf16(X, ldx, dY + k Cout, 8 Cout, nullptr, n, n, 1, Cin, Cout, dW + k Cin Cout, ...) runs, on the
+// row split wgrad_plan_bf16 gives for ONE tap: every (tap, tile, slice) workgroup does what it does there, the workspace is laid out
+// [slice][8][Cin][Cout] and wgrad_reduce adds the slices of every element in the same order -- bit-identical to the eight launches.
+// Returns 1 (dW untouched, the caller issues the per-tap launches) where a tap would not run k_spconv_wgrad_bf16_big<0, 0> or
+// k_lin_wgrad_small.
+static int gen_wgrad_plan(const float* X, int ldx, const float* dY, int n, int Cin, int Cout, bool have_ws, WgradPlan& p) {
+  if (Cout % 4) return 1;                                   // (every tap's columns 16-byte aligned like tap 0's)
+  p = wgrad_plan_bf16(0, 0, X, ldx, dY, 8 * Cout, n, n, 1, Cin, Cout, have_ws);
+  return (p.kind == 2 || p.kind == 5) ? 0 : 1;
+}
+extern "C" int es_gen_transpose_wgrad_bf16(const float* X, int ldx, const float* dY, int n, int Cin, int Cout, float* dW,
+                                           int accumulate, float* ws, size_t ws_floats, void* stream) {
+  if (n <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  WgradPlan p;
+  if (gen_wgrad_plan(X, ldx, dY, n, Cin, Cout, ws != nullptr, p)) return 1;
+  const size_t nw = (size_t)8 * Cin * Cout;
+  if (p.splits > 1 && ws_floats < (size_t)p.splits * nw) return -5;
+  float* wsk = p.splits > 1 ? ws : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (p.kind == 5)
+    hipLaunchKernelGGL(k_lin_wgrad_small, dim3(8 * (Cin / 64), Cout / 64, p.splits), dim3(256), 0, st, X, ldx, dY, 8 * Cout, n, Cin, Cout,
+                       p.rows_per_split, dW, wsk, accumulate, 8, Cout);
+  else
+    hipLaunchKernelGGL((k_spconv_wgrad_bf16_big<0, 0>), dim3(8 * (Cin / 128), Cout / 128, es_cdiv(p.splits, 8) * 8), dim3(256), 0, st,
+                       (const void*)X, ldx, (const void*)dY, 8 * Cout, (const int*)nullptr, n, n, 8, Cin, Cout, p.rows_per_split, p.splits,
+                       dW, wsk, accumulate, Cout);
+  ES_CHECK_LAUNCH();
+  return wgrad_reduce(ws, p.splits, nw, dW, accumulate, st);
+}
+extern "C" size_t es_gen_transpose_wgrad_workspace_floats(const float* X, int ldx, const float* dY, int n, int Cin, int Cout) {
+  WgradPlan p;
+  if (n <= 0 || Cin <= 0 || Cout <= 0 || gen_wgrad_plan(X, ldx, dY, n, Cin, Cout, true, p)) return 0;
+  return p.splits > 1 ? (size_t)p.splits * 8 * Cin * Cout : 0;
 }
 
 // floats of workspace the weight-gradient launch of this shape wants for its row split (0: a single slice, none needed).

@@ -397,6 +397,11 @@ def _first_write(ptr):
     return acc
 
 
+def _written(ptr):
+    """what _first_write(ptr) would return, without stamping (for a launch that may still decline its operands)"""
+    return 1 if _GRAD_STAMP.get(ptr) == GRAD_EPOCH[0] else 0
+
+
 def _wgrad(name, sw, dW, *args, like=None, acc=None):
     """launch a weight-gradient entry point (`args` = everything between the function name and dW) on stream `sw` with the
     workspace its row split asks for (that stream's 'wgrad' buffer); like: a tensor on the launch's device (None: the current GPU,
@@ -415,6 +420,10 @@ def _wgrad(name, sw, dW, *args, like=None, acc=None):
 
 
 IMG_WGRAD = [os.environ.get('ES_IMG_WGRAD', '1') != '0']     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
+# FCAF3D head backward without the work its result does not need (A/B switch; off: exactly the launches before it existed): the 8 taps of a
+# generative transposed convolution's weight gradient in one launch (es_gen_transpose_wgrad_bf16), the head gradient matrix cleared by the
+# focal-loss launch instead of a zero fill (es_focal_loss_clear, models/dense_heads/fcaf3d_head.py)
+HEAD_BWD_FUSED = [os.environ.get('ES_HEAD_BWD_FUSED', '1') != '0']
 
 
 # Python's cyclic collector and the train loop (round 5, profiles/r5d / r5f_bench_grounding_diag.json: `gc_collections`): a generation-2
@@ -959,9 +968,22 @@ def gen_conv_transpose(x, w):
         dfused = False
         if g is not None and bf and GEN_FUSED[0] and y.g.is_contiguous():      # (n * 8, cout) rows = (n, 8 cout)
             dfused = hip.raw('es_gen_transpose_dgrad_bf16')(P(y.g), P(w.bf16()[0]), n, cin, cout, P(g), _ld(g), acc, s) == 0
+        wfused = False
+        slots = [w.g.data_ptr() + 4 * k * cin * cout for k in range(8)] if w.g is not None else []
+        if (w.g is not None and bf and GEN_FUSED[0] and HEAD_BWD_FUSED[0] and y.g.is_contiguous() and x.d.dtype == torch.float32
+                and len({_written(q) for q in slots}) == 1):        # all eight taps' weight gradients in one launch
+            need = hip.raw('es_gen_transpose_wgrad_workspace_floats')(P(x.d), _ld(x.d), P(y.g), n, cin, cout)
+            ws, nf = stream_ws(sw, 'wgrad', need, y.g) if need else (None, 0)
+            rc = hip.raw('es_gen_transpose_wgrad_bf16')(P(x.d), _ld(x.d), P(y.g), n, cin, cout, P(w.g), _written(slots[0]), P(ws), nf, sw)
+            if rc not in (0, 1):                                     # (1: shape not served, nothing launched -- the per-tap launches)
+                raise hip.HipError(f'es_gen_transpose_wgrad_bf16 failed with status {rc}')
+            wfused = rc == 0
+            if wfused:
+                for q in slots:
+                    _first_write(q)
         for k in range(8):
             gy = y.g.data_ptr() + 4 * k * cout
-            if w.g is not None:
+            if w.g is not None and not wfused:
                 _wgrad('es_spconv_wgrad_bf16' if bf else 'es_spconv_wgrad', sw,
                        w.g.data_ptr() + 4 * k * cin * cout, P(x.d), _ld(x.d), gy, 8 * cout, 0, n, n, 1, cin, cout, like=y.g)
             if dfused:

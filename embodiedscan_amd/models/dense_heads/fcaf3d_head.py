@@ -228,9 +228,10 @@ class FCAF3DHeadRotMat:
             ncol = ho.d.shape[1]
             bbox = torch.empty((n, 12), dtype=torch.float32, device=ho.d.device)
             call('es_reg_decode_fwd', ho.d.data_ptr() + 4, ncol, n, P(self.scales[i].d), P(bbox), _stream())
-            score = torch.empty(n, dtype=torch.float32, device=ho.d.device)
-            call('es_row_max', ho.d.data_ptr() + 4 * 13, ncol, n, self.num_classes, P(score), _stream())
-            score_set = out.cs
+            if i > 0:                                   # (read by the next finer level's _prune only: the finest level's has no reader)
+                score = torch.empty(n, dtype=torch.float32, device=ho.d.device)
+                call('es_row_max', ho.d.data_ptr() + 4 * 13, ncol, n, self.num_classes, P(score), _stream())
+                score_set = out.cs
             levels[i] = dict(cs=out.cs, ho=ho, bbox=bbox, scale=self.scales[i], out=out.F, x=x.F)
         return levels
 
@@ -336,7 +337,10 @@ class FCAF3DHeadRotMat:
             pts = torch.empty((lv['cs'].n, 3), dtype=torch.float32, device=dev)
             call('es_coords_to_points', P(lv['cs'].coords), lv['cs'].n, float(self.voxel_size), P(pts), s)
             lv['points'] = pts
-            lv['dho'] = torch.zeros_like(lv['ho'].d)
+            # gradient of the head output: with HEAD_BWD_FUSED the focal-loss launches below clear the columns around the class block of
+            # their rows (the (sample, level) slices with rows partition every level; es_pos_losses of a sample is queued behind them on the
+            # same stream; es_reg_decode_bwd and the GEMM's backward run after join_side) -- no zero fill of the whole matrix
+            lv['dho'] = torch.empty_like(lv['ho'].d) if E.HEAD_BWD_FUSED[0] else torch.zeros_like(lv['ho'].d)
             lv['dbbox'] = torch.zeros_like(lv['bbox'])
         # phase 1: targets per sample (points of a sample concatenated fine->coarse, fcaf3d_head.py:1595-1600)
         # Samples are independent until the avg_factor below and again after it: odd samples go to the side stream.
@@ -390,7 +394,11 @@ class FCAF3DHeadRotMat:
                 bbs.append(lv['bbox'].data_ptr() + 48 * r0)
                 dbbs.append(lv['dbbox'].data_ptr() + 48 * r0)
                 n = lo[l + 1] - lo[l]
-                if n:
+                if n and E.HEAD_BWD_FUSED[0]:
+                    call('es_focal_loss_clear', hos[l] + 4 * 13, ncol, kt.data_ptr() + 4 * lo[l], n, self.num_classes,
+                         self.focal_gamma, self.focal_alpha, avg.data_ptr() + 4 * b, gscale, dhos[l] + 4 * 13, ncol,
+                         P(partial), loss_cls.data_ptr() + 4 * b, 13, ncol - 13 - self.num_classes, s)
+                elif n:
                     call('es_focal_loss', hos[l] + 4 * 13, ncol, kt.data_ptr() + 4 * lo[l], n, self.num_classes,
                          self.focal_gamma, self.focal_alpha, avg.data_ptr() + 4 * b, gscale, dhos[l] + 4 * 13, ncol,
                          P(partial), loss_cls.data_ptr() + 4 * b, s)

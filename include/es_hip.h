@@ -138,6 +138,14 @@ int es_spconv_bf16_is_fast(int n_in, int ldx, int K, int Cin, int Cout);
 int es_gen_transpose_fwd_bf16(const float* X, int ldx, const void* Wt_bf16, int n, int Cin, int Cout, float* Y, void* stream);
 int es_gen_transpose_dgrad_bf16(const float* dY, const void* Wn_bf16, int n, int Cin, int Cout, float* dX, int ldx,
                                 int accumulate, void* stream);
+/* ... and its weight gradient: dW[k] (+)= X^T dY[:, k Cout .. (k + 1) Cout) for the 8 taps in ONE launch (+ at most one reduction launch),
+ * bit-identical to the eight es_spconv_wgrad_bf16(X, ldx, dY + k Cout, 8 Cout, NULL, n, n, 1, Cin, Cout, dW + k Cin Cout, ...) launches: the
+ * tap is a grid dimension of the kernel a single tap runs, on the row split of ONE tap.  Returns 1 for a shape / alignment it does not serve
+ * (dW untouched: the caller issues the per-tap launches), -5 for a workspace smaller than es_gen_transpose_wgrad_workspace_floats (8 x the
+ * per-tap workspace; 0: a single row slice, none needed).  Without a workspace it runs ONE row slice, like es_spconv_wgrad_bf16. */
+int es_gen_transpose_wgrad_bf16(const float* X, int ldx, const float* dY /* (n, 8*Cout) rows */, int n, int Cin, int Cout,
+                                float* dW /* [8][Cin][Cout] */, int accumulate, float* ws, size_t ws_floats, void* stream);
+size_t es_gen_transpose_wgrad_workspace_floats(const float* X, int ldx, const float* dY, int n, int Cin, int Cout);
 /* run-time tuning switches for A/B measurements: key 1 = ping-pong LDS buffers in the fast bf16 kernels (default 1),
  * key 2 = 256x256 weight-gradient tile for layers with C_in, C_out multiples of 256 and bf16-shadow operands (default 1),
  * key 3 = streaming row-GEMM kernel for K = 1 launches on the identity map (default 1),
@@ -351,6 +359,12 @@ int es_get_targets(const float* points, int N, const int* level_off_host, int n_
 int es_focal_loss(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
                   const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial /* 2048 */,
                   float* loss_out /* accumulated */, void* stream);
+/* es_focal_loss that also stores +0 to the `lead` floats before and the `tail` floats after the class block `grad` points at, in each of
+ * its N gradient rows (lead + C + tail <= ldg): the caller's gradient matrix needs no zero fill.  Loss value and class gradients are
+ * bit-identical to es_focal_loss.  -3: lead / tail out of range. */
+int es_focal_loss_clear(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
+                        const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial /* 2048 */,
+                        float* loss_out /* accumulated */, int lead, int tail, void* stream);
 /* bbox[:, :6] = clamp(exp(scale * reg[:, :6]), 1e-3), bbox[:, 6:] = reg[:, 6:]  (fcaf3d_head.py:1135-1137) */
 int es_reg_decode_fwd(const float* reg, int ldr, int n, const float* scale, float* bbox /* (n,12) */, void* stream);
 /* partial: >= 512 floats of scratch (the Scale gradient is reduced in a fixed order, no atomics) */
