@@ -582,6 +582,251 @@ extern "C" int es_attn_kv_fwd(const float* Q, int ldq, const void* kv, int H, in
   return 0;
 }
 
+// ------------------------------------------------------------------ backward of es_attn_kv_fwd: many query rows, one key / value set
+// The shape is the mirror image of the forward: Lq = P * Q is the long axis (3 072 rows at 12 prompts), there is one key set.
+// k_attn_bwd_dkv re-stages Q and dO from f32 -- converted, and scattered into LDS a second time transposed -- every 32 query rows in
+// each of its ceil(Lk / 64) * H workgroups, for 8 matrix instructions per wave.  Here the QUERY side is treated the way the forward treats
+// the key side: k_attn_kv_bwd_prep converts Q * scale and dO ONCE per call into finished tiles, in both orientations the products
+// consume; k_attn_kv_bwd_dkv keeps its 64 keys' K / V tile resident in LDS and streams those tiles with 16-byte copies, 64 query rows a
+// step in bf16 mode: 16 matrix instructions per wave between the same three barriers, no conversion in the loop.
+// Workspace layout (element type as the mode; nq = ceil(Lq / QS) query steps, QS = 64 in bf16 / 32 in f32 mode -- the parity mode
+// keeps the 32-row step so that its f32 tiles stay inside the 64 KiB of static LDS):
+//   block (h, j) at element (h * nq + j) * 4 * QS * 32:  [Qn QS x 32][dOn QS x 32][Qt 32 x QS][dOt 32 x QS]
+//   Qn[r][d] = cvt(f32(Q[j QS + r][h 32 + d] * scale)), dOn likewise without the scale, Qt / dOt their transposes; rows >= Lq are zeros.
+// dK / dV are deterministic: a (key tile, head) is owned by one workgroup that walks the query steps in ascending order.  dQ is
+// k_attn_bwd_dq with one sample: its workgroups own the query rows already, what they stream is the one key set.
+// Rounding points are those of es_attn_bwd: operands -> operand type, probabilities recomputed from lse in f32, f32 accumulation.
+template <bool BF> struct AbT;
+template <> struct AbT<true> { static constexpr int QS = 64, LDT = 72, EPP = 8; };
+template <> struct AbT<false> { static constexpr int QS = 32, LDT = 33, EPP = 4; };
+
+template <bool BF>
+__global__ __launch_bounds__(256) void k_attn_kv_bwd_prep(const float* __restrict__ Q, int ldq, const float* __restrict__ dO, int ldd,
+                                                          int Lq, float scale, typename AtT<BF>::T* __restrict__ ws) {
+  typedef typename AtT<BF>::T T;
+  constexpr int QS = AbT<BF>::QS;
+  const int j = blockIdx.x, h = blockIdx.y, nq = gridDim.x;
+  T* blk = ws + ((size_t)h * nq + j) * (4 * QS * AT_D);
+  T *Qn = blk, *dOn = blk + QS * AT_D, *Qt = blk + 2 * QS * AT_D, *dOt = blk + 3 * QS * AT_D;
+  for (int e = threadIdx.x; e < QS * 8; e += 256) {
+    const int r = e >> 3, c = (e & 7) * 4, q = j * QS + r;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), g = a;
+    if (q < Lq) {
+      a = *(const float4*)(Q + (size_t)q * ldq + h * AT_D + c);
+      g = *(const float4*)(dO + (size_t)q * ldd + h * AT_D + c);
+    }
+    const float av[4] = {a.x * scale, a.y * scale, a.z * scale, a.w * scale}, gv[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const T qa = at_cvt<BF>(av[i]), ga = at_cvt<BF>(gv[i]);
+      Qn[r * AT_D + c + i] = qa;
+      dOn[r * AT_D + c + i] = ga;
+      Qt[(c + i) * QS + r] = qa;
+      dOt[(c + i) * QS + r] = ga;
+    }
+  }
+}
+
+// dst [rows][ldd] <- the dense finished tile src [rows][cols] (16-byte pieces; f32 LDS rows are not 16-byte aligned: scalar stores)
+template <bool BF>
+__device__ inline void copy_tile(typename AtT<BF>::T* dst, int ldd, const typename AtT<BF>::T* __restrict__ src, int rows, int cols) {
+  constexpr int EPP = AbT<BF>::EPP;
+  const int ppr = cols / EPP;
+  for (int e = threadIdx.x; e < rows * ppr; e += 256) {
+    const int r = e / ppr, c = (e - r * ppr) * EPP;
+    if constexpr (BF) {
+      *(uint4*)(dst + r * ldd + c) = *(const uint4*)(src + (size_t)r * cols + c);
+    } else {
+      const float4 v = *(const float4*)(src + (size_t)r * cols + c);
+      float* d = dst + r * ldd + c;
+      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+  }
+}
+
+// grid (ceil(Lk / 64), H).  Wave w owns keys kbase + 16 w .. + 15.
+template <bool BF>
+__global__ __launch_bounds__(256) void k_attn_kv_bwd_dkv(const float* __restrict__ K, int ldk, const float* __restrict__ V, int ldv,
+                                                         const typename AtT<BF>::T* __restrict__ ws, const float* __restrict__ lse,
+                                                         const float* __restrict__ delta, int Lq, int Lk, float* __restrict__ dK,
+                                                         int ldgk, float* __restrict__ dV, int ldgv, int accumulate) {
+  typedef typename AtT<BF>::T T;
+  constexpr int LD = AtT<BF>::LD, QS = AbT<BF>::QS, LDT = AbT<BF>::LDT;
+  __shared__ __attribute__((aligned(16))) T Ks[AT_R * LD], Vs[AT_R * LD], Qs[QS * LD], dOs[QS * LD], Qt[AT_D * LDT], dOt[AT_D * LDT],
+      PTs[AT_R * LDT], dSTs[AT_R * LDT];
+  __shared__ float lseS[QS], delS[QS];
+  const int h = blockIdx.y, kbase = blockIdx.x * AT_R;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, kq = lane >> 4;
+  const int nq = (Lq + QS - 1) / QS;
+  tf32x4_t dk[2], dv[2];
+  dk[0] = dk[1] = dv[0] = dv[1] = (tf32x4_t){0.f, 0.f, 0.f, 0.f};
+  stage_rows<BF>(Ks, K + h * AT_D, ldk, kbase, Lk, AT_R, 1.f);          // resident for the whole query walk
+  stage_rows<BF>(Vs, V + h * AT_D, ldv, kbase, Lk, AT_R, 1.f);
+  for (int j = 0; j < nq; ++j) {
+    const T* blk = ws + ((size_t)h * nq + j) * (4 * QS * AT_D);
+    __syncthreads();                                                   // the previous step's readers are done (and Ks / Vs are staged)
+    copy_tile<BF>(Qs, LD, blk, QS, AT_D);
+    copy_tile<BF>(dOs, LD, blk + QS * AT_D, QS, AT_D);
+    copy_tile<BF>(Qt, LDT, blk + 2 * QS * AT_D, AT_D, QS);
+    copy_tile<BF>(dOt, LDT, blk + 3 * QS * AT_D, AT_D, QS);
+    if (threadIdx.x < QS) {
+      const int q = j * QS + threadIdx.x;
+      lseS[threadIdx.x] = q < Lq ? lse[(size_t)h * Lq + q] : INFINITY;   // exp(s - inf) = 0 for padding rows
+      delS[threadIdx.x] = q < Lq ? delta[(size_t)h * Lq + q] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < QS / 16; ++t) {                                // S^T / dP^T tiles: rows = this wave's 16 keys, cols = 16 queries
+      tf32x4_t st = (tf32x4_t){0.f, 0.f, 0.f, 0.f}, dpt = st;
+      st = tile_mma<BF>(Ks + (wv * 16 + li) * LD, Qs + (t * 16 + li) * LD, kq, st);
+      dpt = tile_mma<BF>(Vs + (wv * 16 + li) * LD, dOs + (t * 16 + li) * LD, kq, dpt);
+      const float lq = lseS[t * 16 + li], dq_ = delS[t * 16 + li];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool ok = (kbase + wv * 16 + kq * 4 + r) < Lk;
+        const float p = ok ? __expf(st[r] - lq) : 0.f;
+        PTs[(wv * 16 + kq * 4 + r) * LDT + t * 16 + li] = at_cvt<BF>(p);
+        dSTs[(wv * 16 + kq * 4 + r) * LDT + t * 16 + li] = at_cvt<BF>(p * (dpt[r] - dq_));
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < QS / 32; ++kk) {                             // reduction over the step's queries, 32 at a time, ascending
+#pragma unroll
+      for (int nf = 0; nf < 2; ++nf) {
+        dv[nf] = tile_mma<BF>(PTs + (wv * 16 + li) * LDT + kk * 32, dOt + (nf * 16 + li) * LDT + kk * 32, kq, dv[nf]);
+        dk[nf] = tile_mma<BF>(dSTs + (wv * 16 + li) * LDT + kk * 32, Qt + (nf * 16 + li) * LDT + kk * 32, kq, dk[nf]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int k = kbase + wv * 16 + kq * 4 + r;
+    if (k >= Lk) continue;
+    float* gk = dK + (size_t)k * ldgk + h * AT_D;
+    float* gv = dV + (size_t)k * ldgv + h * AT_D;
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf) {
+      gk[nf * 16 + li] = accumulate ? gk[nf * 16 + li] + dk[nf][r] : dk[nf][r];     // Qt already carries `scale`
+      gv[nf * 16 + li] = accumulate ? gv[nf * 16 + li] + dv[nf][r] : dv[nf][r];
+    }
+  }
+}
+
+extern "C" size_t es_attn_kv_bwd_workspace_bytes(int H, int Lq, int bf16) {
+  if (H <= 0 || Lq <= 0) return 0;
+  const int QS = bf16 ? AbT<true>::QS : AbT<false>::QS;
+  return (size_t)H * es_cdiv(Lq, QS) * 4 * QS * AT_D * (bf16 ? 2 : 4);
+}
+extern "C" int es_attn_kv_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
+                              const float* dO, int ldd, const float* lse, int H, int Lq, int Lk, float* delta_scratch, void* workspace,
+                              size_t workspace_bytes, float* dQ, int ldgq, float* dK, int ldgk, float* dV, int ldgv, int accumulate,
+                              int bf16, void* stream) {
+  if (H <= 0 || Lq <= 0 || Lk <= 0) return 0;
+  if ((ldq | ldk | ldv | ldo | ldd | ldgq | ldgk | ldgv) & 3) return -3;
+  if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < es_attn_kv_bwd_workspace_bytes(H, Lq, bf16)) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  const float scale = 0.17677669529663687f;
+  hipLaunchKernelGGL(k_attn_delta, dim3(es_cdiv((long long)H * Lq, 256)), dim3(256), 0, st, O, ldo, dO, ldd, 1, H, Lq, delta_scratch);
+  dim3 gq(es_cdiv(Lq, AT_R), H, 1), gk(es_cdiv(Lk, AT_R), H);
+  if (bf16) {
+    hipLaunchKernelGGL(k_attn_kv_bwd_prep<true>, dim3(es_cdiv(Lq, AbT<true>::QS), H), dim3(256), 0, st, Q, ldq, dO, ldd, Lq, scale,
+                       (unsigned short*)workspace);
+    hipLaunchKernelGGL(k_attn_bwd_dq<true>, gq, dim3(256), 0, st, Q, ldq, K, ldk, V, ldv, dO, ldd, lse, delta_scratch, Lq, Lk,
+                       (const int*)nullptr, scale, dQ, ldgq, accumulate, H);
+    hipLaunchKernelGGL(k_attn_kv_bwd_dkv<true>, gk, dim3(256), 0, st, K, ldk, V, ldv, (const unsigned short*)workspace, lse,
+                       delta_scratch, Lq, Lk, dK, ldgk, dV, ldgv, accumulate);
+  } else {
+    hipLaunchKernelGGL(k_attn_kv_bwd_prep<false>, dim3(es_cdiv(Lq, AbT<false>::QS), H), dim3(256), 0, st, Q, ldq, dO, ldd, Lq, scale,
+                       (float*)workspace);
+    hipLaunchKernelGGL(k_attn_bwd_dq<false>, gq, dim3(256), 0, st, Q, ldq, K, ldk, V, ldv, dO, ldd, lse, delta_scratch, Lq, Lk,
+                       (const int*)nullptr, scale, dQ, ldgq, accumulate, H);
+    hipLaunchKernelGGL(k_attn_kv_bwd_dkv<false>, gk, dim3(256), 0, st, K, ldk, V, ldv, (const float*)workspace, lse, delta_scratch, Lq,
+                       Lk, dK, ldgk, dV, ldgv, accumulate);
+  }
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ gather backward with rows shared between prompts
+// (SparseFeatureFusion3DGrounder.loss_shared: the query rows of P prompts are gathered from ONE scene's L token rows, and different
+// prompts select overlapping rows -- es_row_move mode 1, a plain `+=`, would race on them.)  Two launches, no float atomics:
+//   k_scatter_table: workgroup p clears row p of the (P, L) position table to -1 and then writes pos[p][idx[p][q]] = q.  The indices
+//     of one prompt are distinct (top-k), so no two lanes write one slot, and nobody but workgroup p touches row p;
+//   k_scatter_sum: one lane per (scene row l, channel quad) walks p upward: s = +0, s += dy[p*Q + pos[p][l]] for the prompts that
+//     selected l.  The order of the additions is the order of p -- the result is a function of the inputs alone.
+// Indices outside [0, L) select nothing (as es_row_move skips negative rows).
+__global__ __launch_bounds__(256) void k_scatter_table(const int* __restrict__ idx, int Q, int L, int* __restrict__ pos) {
+  const int p = blockIdx.x;
+  int* row = pos + (size_t)p * L;
+  for (int l = threadIdx.x; l < L; l += 256) row[l] = -1;
+  __syncthreads();
+  for (int q = threadIdx.x; q < Q; q += 256) {
+    int l = idx[(size_t)p * Q + q];
+    if (l >= 0 && l < L) row[l] = q;
+  }
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void k_scatter_sum(const float* __restrict__ dy, int ldy, const int* __restrict__ pos, int P, int Q,
+                                                     int L, int Cv, float* __restrict__ dx, int ldx, int accumulate) {
+  const size_t tot = (size_t)L * Cv;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (size_t)gridDim.x * 256) {
+    const int l = (int)(e / Cv), c = (int)(e - (size_t)l * Cv) * VEC;
+    float s[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+    for (int p = 0; p < P; ++p) {
+      const int q = pos[(size_t)p * L + l];
+      if (q < 0) continue;
+      const float* src = dy + ((size_t)p * Q + q) * ldy + c;
+      if constexpr (VEC == 4) {
+        const float4 v = *(const float4*)src;
+        s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
+      } else {
+        s[0] += src[0];
+      }
+    }
+    float* dst = dx + (size_t)l * ldx + c;
+    if constexpr (VEC == 4) {
+      float4 o = make_float4(s[0], s[1], s[2], s[3]);
+      if (accumulate) {
+        const float4 a = *(const float4*)dst;
+        o = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
+      }
+      *(float4*)dst = o;
+    } else {
+      dst[0] = accumulate ? dst[0] + s[0] : s[0];
+    }
+  }
+}
+extern "C" size_t es_rows_scatter_sum_workspace_ints(int P, int L) {
+  if (P <= 0 || L <= 0) return 0;
+  return (size_t)P * L;
+}
+extern "C" int es_rows_scatter_sum(const float* dy, int ldy, const int* idx, int P, int Q, int L, int C, float* dx, int ldx,
+                                   int accumulate, int* workspace, size_t workspace_ints, void* stream) {
+  if (P < 0 || Q < 0 || L <= 0 || C <= 0) return 0;
+  if (Q > L) return -4;                                     // distinct rows per prompt: at most L of them
+  if (ldy < C || ldx < C) return -3;
+  const bool vec = (C % 4 == 0) && (((((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0);
+  if (vec && ((ldy | ldx) & 3)) return -3;
+  if (P > 0 && (!workspace || workspace_ints < es_rows_scatter_sum_workspace_ints(P, L))) return -5;
+  if ((long long)P * Q > 0x7fffffffLL) return -4;
+  if (P > 0) {
+    hipLaunchKernelGGL(k_scatter_table, dim3(P), dim3(256), 0, (hipStream_t)stream, idx, Q, L, workspace);
+    ES_CHECK_LAUNCH();
+  }
+  const int Cv = vec ? C / 4 : C;
+  int g = es_cdiv((long long)L * Cv, 256);
+  if (g > 8192) g = 8192;
+  if (vec)
+    hipLaunchKernelGGL(k_scatter_sum<4>, dim3(g), dim3(256), 0, (hipStream_t)stream, dy, ldy, workspace, P, Q, L, Cv, dx, ldx, accumulate);
+  else
+    hipLaunchKernelGGL(k_scatter_sum<1>, dim3(g), dim3(256), 0, (hipStream_t)stream, dy, ldy, workspace, P, Q, L, Cv, dx, ldx, accumulate);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ LayerNorm over the channel dim of (n, C) rows
 // z = x (+ res); y = (z - mean) * rstd * w + b.  One wave per row, C <= 512.  z is written out when res != NULL (backward
 // needs the normalised input); mean / rstd saved per row.

@@ -1155,6 +1155,64 @@ def gather_rows(x, idx):
     return y
 
 
+def gather_rows_shared(x, idx, P_, Q, r0=0, L=None):
+    """y (P_*Q, C) = x[r0 + idx] for P_ prompts' (P_, Q) int32 row choices among ONE scene's rows [r0, r0 + L) of x (default: all of x):
+    different prompts select overlapping rows, so the backward is es_rows_scatter_sum (per row the prompts' gradients added in ascending
+    prompt order, no atomics) instead of es_row_move's plain `+=`.  The indices of one prompt must be distinct (es_topk_sorted
+    guarantees it)."""
+    C = x.d.shape[1]
+    L = x.d.shape[0] - r0 if L is None else L
+    n = P_ * Q
+    assert idx.dtype == torch.int32 and idx.numel() == n and idx.is_contiguous() and 0 <= r0 and r0 + L <= x.d.shape[0]
+    y = Var(empty((n, C), x.d))
+    xs = x.d[r0:r0 + L]
+    call('es_row_move', P(y.d), C, P(xs), _ld(x.d), P(idx), n, C, 0, _stream())
+
+    def bwd():
+        if y.g is None or not x.rg:
+            return
+        if x.g is None:
+            x.g = torch.zeros_like(x.d)         # (the scenes of a batch write disjoint row ranges; rows between them stay zero)
+        x.gh = None
+        g = x.g[r0:r0 + L]
+        nws = int(hip.raw('es_rows_scatter_sum_workspace_ints')(P_, L))
+        ws = torch.empty(max(nws, 1), dtype=torch.int32, device=x.d.device)
+        rec = None
+        if DEBUG_OPS is not None:
+            rec = dict(kind='scatter_sum', dy=y.g.clone(), idx=idx.clone(), P=P_, Q=Q, L=L, C=C, acc=1, dx0=g.clone())
+            DEBUG_OPS.append(rec)
+        call('es_rows_scatter_sum', P(y.g), _ld(y.g), P(idx), P_, Q, L, C, P(g), _ld(g), 1, P(ws), nws, _stream())
+        if rec is not None:
+            rec['dx1'] = g.clone()
+    TAPE.add(bwd)
+    return y
+
+
+def concat_rows(vs):
+    """the rows of the Vars `vs` (same width) one after the other; each input's gradient is its row range of the result's"""
+    if len(vs) == 1:
+        return vs[0]
+    y = Var(torch.cat([v.d for v in vs]))
+    offs = [0]
+    for v in vs:
+        offs.append(offs[-1] + v.d.shape[0])
+
+    def bwd():
+        if y.g is None:
+            return
+        for i, v in enumerate(vs):
+            if not v.rg:
+                continue
+            part = y.g[offs[i]:offs[i + 1]]
+            if v.g is None:
+                v.g = part
+            else:
+                call('es_axpy2d', P(v.g), _ld(v.g), P(part), _ld(y.g), part.shape[0], part.shape[1], 1.0, 1, _stream())
+            v.gh = None
+    TAPE.add(bwd)
+    return y
+
+
 def union_add(a, b, pos_a, pos_b, n):
     """sparse a + b on the coordinate union (rows pos_a / pos_b of the result)."""
     C = a.d.shape[1]
@@ -1339,34 +1397,90 @@ def attention(q, k, v, B, H, Lq, Lk, klen=None):
     return o
 
 
-# ---- one scene, many prompts (SparseFeatureFusion3DGrounder.ground): forward only, nothing on the tape
+# ---- one scene, many prompts: forward only for SparseFeatureFusion3DGrounder.ground (nothing on the tape), taped for loss_shared
+# backward of the taped attention_kv: es_attn_kv_bwd (the query side converted once per call, the workgroup's key tile resident) or
+# es_attn_bwd with B = 1 -- the same function (A/B switch; the default follows the decision in DESIGN section 3c, tools/bench_shared_train.py)
+ATTN_KV_BWD = [os.environ.get('ES_ATTN_KV_BWD', '1') != '0']
+
+
 class PreparedKV:
     """the projected keys / values of one cross-attention layer in the operand image es_attn_kv_fwd consumes (csrc/transformer.hip),
-    built once per scene; k / v: the f32 projections, kept only when DEBUG_FWD was set at build time (the forward record needs them)"""
-    __slots__ = ('kv', 'H', 'Lk', 'bf', 'k', 'v')
+    built once per scene; k / v: the f32 projections, kept only when DEBUG_FWD was set at build time (the forward record needs them).
+    Taped form (attention_kv_prepare(..., src=...)): kvar / vvar are the projection Vars the scene's rows [r0, r0 + Lk) were taken from
+    and `group` the state the scenes of one layer share (their gradient buffers are made once, by whichever scene's backward runs first)"""
+    __slots__ = ('kv', 'H', 'Lk', 'bf', 'k', 'v', 'kvar', 'vvar', 'r0', 'group')
 
 
-def attention_kv_prepare(k, v, H, Lk):
-    """k / v: Vars (Lk, H*32), the projected point tokens of one scene -> PreparedKV in the precision of the current mode"""
+def attention_kv_prepare(k, v, H, Lk, src=None):
+    """k / v: Vars (Lk, H*32), the projected point tokens of one scene -> PreparedKV in the precision of the current mode.
+    src = (kvar, vvar, r0, group): k / v are rows [r0, r0 + Lk) of these projection Vars (several scenes' padded rows), which receive the
+    gradients of a taped attention_kv; group: a dict shared by the scenes of one layer"""
     bf = 1 if PRECISION[0] == 'bf16' else 0
     pk = PreparedKV()
     pk.H, pk.Lk, pk.bf = H, Lk, bf
     pk.kv = torch.empty(int(hip.raw('es_attn_kv_bytes')(H, Lk, bf)), dtype=torch.uint8, device=k.d.device)
     call('es_attn_kv_prepare', P(k.d), _ld(k.d), P(v.d), _ld(v.d), H, Lk, bf, P(pk.kv), _stream())
-    pk.k, pk.v = (k.d, v.d) if DEBUG_FWD is not None else (None, None)
+    pk.k, pk.v = (k.d, v.d) if (DEBUG_FWD is not None or src is not None) else (None, None)
+    pk.kvar, pk.vvar, pk.r0, pk.group = src if src is not None else (None, None, 0, None)
     return pk
 
 
 def attention_kv(q, pk, Lq):
-    """softmax(q k^T / sqrt(32)) v per head of Lq query rows (any number of prompts' queries) over the ONE prepared key / value set"""
-    H, Lk = pk.H, pk.Lk
-    o = Var(empty((Lq, H * 32), q.d), rg=False)
-    lse = empty((H * Lq,), q.d)
-    call('es_attn_kv_fwd', P(q.d), _ld(q.d), P(pk.kv), H, Lq, Lk, P(o.d), H * 32, P(lse), pk.bf, _stream())
-    if DEBUG_FWD is not None:
-        if pk.k is None:
-            raise RuntimeError('DEBUG_FWD: this scene encoding was built without it (the record needs the f32 projections): rebuild it')
-        fwd_record('attention', 'es_attn_kv_fwd', q=q.d, k=pk.k, v=pk.v, B=1, H=H, Lq=Lq, Lk=Lk, klen=None, bf=pk.bf, o=o.d, lse=lse)
+    """softmax(q k^T / sqrt(32)) v per head of Lq query rows (any number of prompts' queries) over the ONE prepared key / value set.
+    pk may be a list of PreparedKV, one per scene: q then holds Lq rows per scene, scene after scene, and each block attends to its own
+    scene.  With the tape on, a q that requires a gradient and PreparedKVs that kept their projection Vars, the backward is recorded: dQ
+    and each scene's rows of dK / dV by es_attn_kv_bwd (ATTN_KV_BWD off: es_attn_bwd with B = 1) on the f32 projections, same rounding
+    points as the forward."""
+    pks = list(pk) if isinstance(pk, (list, tuple)) else [pk]
+    H = pks[0].H
+    n = len(pks) * Lq
+    taped = TAPE.enabled and q.rg and all(k_.kvar is not None for k_ in pks)
+    o = Var(empty((n, H * 32), q.d), rg=taped)
+    lse = empty((len(pks), H * Lq), q.d)
+    for s_, k_ in enumerate(pks):
+        qs, os_ = q.d[s_ * Lq:(s_ + 1) * Lq], o.d[s_ * Lq:(s_ + 1) * Lq]
+        call('es_attn_kv_fwd', P(qs), _ld(q.d), P(k_.kv), H, Lq, k_.Lk, P(os_), H * 32, P(lse[s_]), k_.bf, _stream())
+        if DEBUG_FWD is not None:
+            if k_.k is None:
+                raise RuntimeError('DEBUG_FWD: this scene encoding was built without it (the record needs the f32 projections): rebuild it')
+            fwd_record('attention', 'es_attn_kv_fwd', q=qs, k=k_.k, v=k_.v, B=1, H=H, Lq=Lq, Lk=k_.Lk, klen=None, bf=k_.bf, o=os_, lse=lse[s_])
+    if not taped:
+        return o
+
+    def bwd():
+        if o.g is None:
+            return
+        assert q.g is None, 'attention_kv: q must be a fresh projection (single consumer)'
+        q.g = torch.empty_like(q.d)
+        delta = empty((len(pks), H * Lq), q.d)
+        for s_, k_ in enumerate(pks):
+            kvar, vvar, r0, group, Lk = k_.kvar, k_.vvar, k_.r0, k_.group, k_.Lk
+            if not group.get('made'):
+                # the scenes of a layer write disjoint row ranges of the projections' gradients; the padded rows between them stay zero
+                assert kvar.g is None and vvar.g is None, 'attention_kv: k / v must be fresh projections (single consumer)'
+                kvar.g, vvar.g = torch.zeros_like(kvar.d), torch.zeros_like(vvar.d)
+                kvar.gh = vvar.gh = None
+                group['made'] = True
+            sl = slice(s_ * Lq, (s_ + 1) * Lq)
+            qs, os_, dos, dq = q.d[sl], o.d[sl], o.g[sl], q.g[sl]
+            dk, dv = kvar.g[r0:r0 + Lk], vvar.g[r0:r0 + Lk]
+            rec = None
+            if DEBUG_OPS is not None:
+                rec = dict(kind='attn', q=qs.clone(), k=k_.k.clone(), v=k_.v.clone(), o=os_.clone(), do=dos.clone(), lse=lse[s_].clone(),
+                           klen=None, B=1, H=H, Lq=Lq, Lk=Lk, bf=k_.bf, acc=0, before=None, shared=True,
+                           entry='es_attn_kv_bwd' if ATTN_KV_BWD[0] else 'es_attn_bwd')
+                DEBUG_OPS.append(rec)
+            if ATTN_KV_BWD[0]:
+                nws = int(hip.raw('es_attn_kv_bwd_workspace_bytes')(H, Lq, k_.bf))
+                ws = torch.empty(nws, dtype=torch.uint8, device=q.d.device)
+                call('es_attn_kv_bwd', P(qs), _ld(q.d), P(k_.k), _ld(k_.k), P(k_.v), _ld(k_.v), P(os_), H * 32, P(dos), _ld(o.g), P(lse[s_]), H,
+                     Lq, Lk, P(delta[s_]), P(ws), nws, P(dq), _ld(q.g), P(dk), _ld(kvar.g), P(dv), _ld(vvar.g), 0, k_.bf, _stream())
+            else:
+                call('es_attn_bwd', P(qs), _ld(q.d), P(k_.k), _ld(k_.k), P(k_.v), _ld(k_.v), P(os_), H * 32, P(dos), _ld(o.g), P(lse[s_]), 1, H,
+                     Lq, Lk, 0, P(delta[s_]), P(dq), _ld(q.g), P(dk), _ld(kvar.g), P(dv), _ld(vvar.g), 0, k_.bf, _stream())
+            if rec is not None:
+                rec.update(delta=delta[s_].clone(), dq=dq.clone(), dk=dk.clone(), dv=dv.clone())
+    TAPE.add(bwd)
     return o
 
 

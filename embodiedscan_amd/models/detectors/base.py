@@ -127,6 +127,10 @@ class DetectorBase:
         E.TAPE.clear()
 
     def train_step(self, data, optim_wrapper):
+        return self._train_step(data, optim_wrapper, lambda inputs, samples: self.forward(inputs, samples, mode='loss'))
+
+    def _train_step(self, data, optim_wrapper, loss_fn):
+        """the body of train_step with the loss forward as a callable (inputs, data_samples) -> loss dict"""
         E.settle_gc(self)
         E.TAPE.clear()
         hip.refresh_stream()
@@ -137,7 +141,7 @@ class DetectorBase:
         self.arena.grad.zero_()
         E.new_grad_epoch()                       # first weight-gradient launch per weight overwrites, later ones add
         self._tape_parts = []
-        losses = self.forward(data['inputs'], data['data_samples'], mode='loss')
+        losses = loss_fn(data['inputs'], data['data_samples'])
         E.mark('forward + losses')
         red = None
         if is_dist():

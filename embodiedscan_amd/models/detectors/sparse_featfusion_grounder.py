@@ -394,3 +394,105 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         if force is not None:
             self.free_queries = torch.cat(free)
         return results
+
+    # ------------------------------------------------------------------ many prompts per scan on one shared scene encoding (training)
+    @staticmethod
+    def _shared_prompts(batch_data_samples):
+        """(the S*P prompt records scan-major, P) of scan-grouped data samples (pipeline.make_shared_grounding_batch); ValueError unless
+        every scan carries the same positive number of prompts"""
+        flat, P_ = [], None
+        for i, ds in enumerate(batch_data_samples):
+            pr = getattr(ds, 'prompts', None)
+            if not pr:
+                raise ValueError(f'data sample {i} carries no `prompts` (see pipeline.make_shared_grounding_batch)')
+            if P_ is None:
+                P_ = len(pr)
+            elif len(pr) != P_:
+                raise ValueError(f'unequal prompts per scan: sample 0 carries {P_}, sample {i} carries {len(pr)}; loss_shared is defined '
+                                 f'for equal counts only (datasets.ScanGroupedGrounding always yields them)')
+            flat += list(pr)
+        if P_ is None:
+            raise ValueError('empty batch')
+        return flat, P_
+
+    def _shared_transformer(self, feats, coords, lens, Lmax, text, tlen, T, P_):
+        """forward_transformer for S scenes x P_ prompts (sample (s, p) = block s*P_ + p of the text / query rows) without the P_ copies
+        of a scene's tokens: query selection by es_contrastive_shared_fwd per scene (bit-identical to the replicated form) + es_topk_sorted,
+        gather_rows_shared, decoder.forward_shared_train"""
+        S = len(lens)
+        dev = feats.d.device
+        s = hip.stream()
+        Q = min(self.num_queries, min(lens))
+        idx = torch.empty((S * P_, Q), dtype=torch.int32, device=dev)
+        klen = torch.tensor([n for n in lens for _ in range(P_)], dtype=torch.int32).to(dev, non_blocking=True)
+        rowmaxes = []
+        for sc in range(S):
+            rows = feats.d[sc * Lmax:sc * Lmax + lens[sc]]
+            _, rowmax = self.bbox_head.cls_branch_shared(rows, E.Var(text.d[sc * P_ * T:(sc + 1) * P_ * T], rg=False), P_, T,
+                                                         tlen[sc * P_:(sc + 1) * P_])
+            call('es_topk_sorted', P(rowmax), P_, lens[sc], P(klen[sc * P_:(sc + 1) * P_]), Q, P(idx[sc * P_:(sc + 1) * P_]), s)
+            rowmaxes.append(rowmax)
+        if getattr(self, 'force_queries', None) is not None:     # test hook (teacher forcing), shape (S*P_, Q): see forward_transformer
+            self.free_queries = idx
+            idx = self.force_queries.to(device=dev, dtype=torch.int32).reshape(S * P_, Q).contiguous()
+        off = (torch.arange(S, device=dev, dtype=torch.int32) * Lmax).repeat_interleave(P_)
+        gidx = (idx + off[:, None]).reshape(-1).contiguous()
+        query = E.concat_rows([E.gather_rows_shared(feats, idx[sc * P_:(sc + 1) * P_], P_, Q, r0=sc * Lmax, L=lens[sc]) for sc in range(S)])
+        qcoords = torch.empty((S * P_ * Q, 3), dtype=torch.float32, device=dev)
+        call('es_row_move', P(qcoords), 3, P(coords), 3, P(gidx), S * P_ * Q, 3, 0, s)
+        prev = E.TAPE.enabled
+        E.TAPE.enabled = False                   # proposals: reg_branches[num_layers] on the selected tokens, detached
+        try:
+            pred0 = self.bbox_head.decode(qcoords, self.bbox_head.reg_branch(E.Var(query.d, rg=False))).d
+        finally:
+            E.TAPE.enabled = prev
+        self.last_queries = dict(idx=idx, gidx=gidx, rowmax=rowmaxes, pred0=pred0, Q=Q, klen=klen)
+        return self.decoder.forward_shared_train(query, feats, coords, list(lens), Lmax, qcoords, pred0, text, S, P_, Q, T, tlen,
+                                                 self.bbox_head)
+
+    def loss_shared(self, batch_inputs_dict, batch_data_samples, **kwargs):
+        """`loss` on the replicated batch -- S scans with P prompts each as the S*P samples in which scan s appears P times, scan-major --
+        without the copies: one data sample per scan carrying `prompts` (P records with text, tokens_positive, gt_instances_3d).  The 2-D
+        backbone, voxelisation, the sparse backbone, the fusion and MinkNeck run once per scan, forward and backward; the loss dict is built by
+        the same normalisation over S*P samples and the parameter gradients are the replicated batch's up to the order of floating-point
+        sums (train-mode BatchNorm included: P copies of every row change neither mean nor biased variance).  Unequal P: ValueError."""
+        prompts, P_ = self._shared_prompts(batch_data_samples)   # (refused before anything is launched)
+        self._bind()
+        job = self.start_text(prompts)
+        self.extract_feat(batch_inputs_dict, batch_data_samples)
+        E.mark('A19 MinkNeck (+ pruning, token padding)')
+        text, mask, tlen, T = self.finish_text(job, prompts)
+        E.mark('A19 frozen text encoder + text_feat_map')
+        nk = self.neck_3d.last
+        hidden, boxes = self._shared_transformer(nk['feats'], nk['points'], nk['lens'], nk['Lmax'], text, tlen, T, P_)
+        E.mark('A19 query selection + 6-layer decoder')
+        out = self.bbox_head.loss(hidden, boxes, text, mask, prompts, tlen=tlen)
+        E.mark('A19/N2 head: token logits + Hungarian + focal + corner-Chamfer')
+        return out
+
+    def loss_shared_from_tokens(self, feats, points, lens, prompts):
+        """loss_shared from MinkNeck tokens (the counterpart of scene_from_tokens): feats engine.Var (S*Lmax, E) that requires a gradient
+        (zero rows behind each scene's lens[s] rows), points (S*Lmax, 3), lens the S token counts, prompts the S*P records scan-major.
+        The prompt side, forward and backward, without the backbones; the caller runs the tape (engine.TAPE.backward())."""
+        S = len(lens)
+        if S < 1 or len(prompts) % S or not prompts:
+            raise ValueError(f'{len(prompts)} prompts do not divide over {S} scenes: loss_shared is defined for equal counts per scene only')
+        if feats.d.shape[0] % S or feats.d.shape[1] != self.embed_dims or tuple(points.shape) != (feats.d.shape[0], 3):
+            raise ValueError(f'expected (S*Lmax, {self.embed_dims}) features and (S*Lmax, 3) points, got {tuple(feats.d.shape)} / {tuple(points.shape)}')
+        Lmax = feats.d.shape[0] // S
+        if max(lens) > Lmax or min(lens) < 1:
+            raise ValueError(f'lens {list(lens)} outside [1, Lmax = {Lmax}]')
+        hip.refresh_stream()
+        self._bind()
+        prompts = list(prompts)
+        text, mask, tlen, T = self.encode_text(prompts)
+        hidden, boxes = self._shared_transformer(feats, points, list(lens), Lmax, text, tlen, T, len(prompts) // S)
+        return self.bbox_head.loss(hidden, boxes, text, mask, prompts, tlen=tlen)
+
+    def train_step_shared(self, data, optim_wrapper):
+        """train_step with loss_shared: data from pipeline.make_shared_grounding_batch (one sample per scan, P prompts each)"""
+        def loss_fn(inputs, samples):
+            hip.refresh_stream()
+            return self.loss_shared(inputs, samples)
+        self._shared_prompts(data['data_samples'])               # unequal P: refused before the step touches anything
+        return self._train_step(data, optim_wrapper, loss_fn)

@@ -320,6 +320,11 @@ class SparseFeatureFusionSingleStage3DDetector:
 
     def train_step(self, data, optim_wrapper):
         """mmengine BaseModel.train_step: preprocess, loss forward, sum of the 'loss' entries, backward, update."""
+        return self._train_step(data, optim_wrapper, lambda inputs, samples: self.forward(inputs, samples, mode='loss'))
+
+    def _train_step(self, data, optim_wrapper, loss_fn):
+        """the body of train_step with the loss forward as a callable (inputs, data_samples) -> loss dict (the grounder's
+        train_step_shared passes loss_shared)"""
         E.settle_gc(self)                        # (the collector's generations are frozen once the warm-up steps are through)
         E.TAPE.clear()
         hip.refresh_stream()
@@ -332,7 +337,7 @@ class SparseFeatureFusionSingleStage3DDetector:
         self._bind()
         self.arena.grad.zero_()
         E.new_grad_epoch()                       # first weight-gradient launch per weight overwrites, later ones add
-        losses = self.forward(data['inputs'], data['data_samples'], mode='loss')
+        losses = loss_fn(data['inputs'], data['data_samples'])
         E.mark('A10-A16 head fwd + targets + losses')
         if is_dist():
             # bucketed gradient all-reduce overlapped with backward: markers fire when the tape (run in reverse) has

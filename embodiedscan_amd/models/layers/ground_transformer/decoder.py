@@ -82,8 +82,13 @@ class _MHA:
         """the key side alone: (k_in Wk + bk, v_in Wv + bv)"""
         return E.linear(k_in, self.wk, self.bias[1], need_dx=False), E.linear(v_in, self.wv, self.bias[2], need_dx=False)
 
+    def project_kv_train(self, k_in, v_in):
+        """project_kv with the gradients of the inputs and the weights recorded (forward_shared_train)"""
+        return E.linear(k_in, self.wk, self.bias[1]), E.linear(v_in, self.wv, self.bias[2])
+
     def on_prepared(self, query, q_in, prepared, Lq):
-        """__call__ with the key side taken from an engine.PreparedKV (one scene's point tokens, any number of prompts' queries)"""
+        """__call__ with the key side taken from an engine.PreparedKV (one scene's point tokens, any number of prompts' queries) or from
+        a list of them, one per scene with Lq query rows each"""
         q = E.linear(q_in, self.wq, self.bias[0])
         return self.out(E.attention_kv(q, prepared, Lq)), query
 
@@ -110,7 +115,8 @@ class DecoderLayer:
         if prepared is None:
             a, idt = self.cross_attn(query, qp, key_with_pos, key, B, Q, Lk, klen)
         else:
-            a, idt = self.cross_attn.on_prepared(query, qp, prepared, B * Q)
+            n_scene = len(prepared) if isinstance(prepared, (list, tuple)) else 1
+            a, idt = self.cross_attn.on_prepared(query, qp, prepared, B * Q // n_scene)
         query = self.norms[2](a, res=idt)
         h = E.relu_(self.ffn0(query))
         return self.norms[3](self.ffn1(h), res=query)
@@ -173,6 +179,33 @@ class SparseFeatureFusionTransformerDecoder:
         for layer, pk in zip(self.layers, prepared):
             query_pos = self.self_posembed(pred_bboxes, False)
             query = layer(query, query_pos, None, None, text, P, Q, pk.Lk, T, None, tlen, prepared=pk)
+            new_boxes = bbox_head.decode(query_coords, bbox_head.reg_branch(query))
+            pred_bboxes = new_boxes.d
+            inter.append(self.norm(query))
+            boxes.append(new_boxes)
+        return inter, boxes
+
+    def forward_shared_train(self, query, key, key_coords, lens, Lmax, query_coords, pred_bboxes, text, S, P, Q, T, tlen, bbox_head):
+        """forward() for S scenes with P prompts each WITHOUT the P copies of a scene's key side, on the tape: query Var (S*P*Q, E) (sample
+        (s, p) = block s*P + p), key Var (S*Lmax, E) padded, key_coords (S*Lmax, 3), lens the scenes' token counts, text Var (S*P*T, E).
+        cross_posembed runs once on the padded buffer (its train-mode BatchNorm sees the padded rows, as in forward(); P copies of every row
+        change neither mean nor biased variance), K / V are projected once per layer on the S*Lmax rows, es_attn_kv_prepare runs per scene
+        on its lens[s] live rows, self-attention and the text cross-attention run with B = S*P and the point cross-attention of scene s's
+        P*Q query rows on scene s's prepared operands.  Same return as forward()."""
+        tr = self.training
+        key_pos = self.cross_posembed(key_coords, tr, repeat=self.num_layers)
+        key_with_pos = E.add(key, key_pos)
+        inter, boxes = [], []
+        for layer in self.layers:
+            k, v = layer.cross_attn.project_kv_train(key_with_pos, key)
+            group = {}
+            prepared = []
+            for s in range(S):
+                r0, n = s * Lmax, lens[s]
+                prepared.append(E.attention_kv_prepare(E.Var(k.d[r0:r0 + n], rg=False), E.Var(v.d[r0:r0 + n], rg=False), self.num_heads, n,
+                                                       src=(k, v, r0, group)))
+            query_pos = self.self_posembed(pred_bboxes, tr)
+            query = layer(query, query_pos, None, None, text, S * P, Q, Lmax, T, None, tlen, prepared=prepared)
             new_boxes = bbox_head.decode(query_coords, bbox_head.reg_branch(query))
             pred_bboxes = new_boxes.d
             inter.append(self.norm(query))

@@ -86,7 +86,7 @@ def _host_tensors(scan):
 def _finish(d, scan):
     d.update(meta=scan['meta'], gt_boxes=torch.as_tensor(scan['gt_boxes']), gt_labels=torch.as_tensor(scan['gt_labels']))
     for k in ('gt_occupancy', 'gt_occupancy_masks', 'visible_occupancy_masks', 'visible_instance_masks', 'point_range',
-              'text', 'tokens_positive', 'draw', 'points_slice_indices'):
+              'text', 'tokens_positive', 'prompts', 'draw', 'points_slice_indices'):
         if k in scan:
             d[k] = scan[k]
     return d
@@ -328,6 +328,32 @@ def make_grounding_batch(dscans, anns=None):
         ds.text, ds.tokens_positive = a['text'], a['tokens_positive']
         ds.gt_instances_3d = InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(torch.as_tensor(a['gt_boxes'])),
                                           labels_3d=torch.as_tensor(a['gt_labels']))
+    return data
+
+
+class GroundingPrompt:
+    """one prompt of a scan-grouped grounding sample: what the text encoder, the positive maps and GroundingHead.loss read of a data sample
+    (text, tokens_positive, gt_instances_3d) + the three eval flags"""
+
+    def __init__(self, text, tokens_positive, gt_boxes, gt_labels, is_view_dep=None, is_hard=None, is_unique=None):
+        self.text, self.tokens_positive = text, tokens_positive
+        self.gt_instances_3d = InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(torch.as_tensor(gt_boxes)), labels_3d=torch.as_tensor(gt_labels))
+        self.is_view_dep, self.is_hard, self.is_unique = is_view_dep, is_hard, is_unique
+
+
+def make_shared_grounding_batch(dscans, prompt_anns=None):
+    """`data` dict for SparseFeatureFusion3DGrounder.train_step_shared: the detection batch of the S scans, ONE data sample per scan, each
+    carrying `prompts`: P GroundingPrompt records.  prompt_anns[s]: the P annotation dicts of scan s with the keys make_grounding_batch
+    takes (text, tokens_positive, gt_boxes, gt_labels; optionally the eval flags); None: scans from datasets.ScanGroupedGrounding carry
+    them as `prompts`.  Every scan must carry the same number of prompts (loss_shared refuses anything else)."""
+    data = make_batch(dscans)
+    if prompt_anns is None:
+        prompt_anns = [d['prompts'] for d in dscans]
+    if len(prompt_anns) != len(dscans):
+        raise ValueError(f'{len(dscans)} scans but {len(prompt_anns)} prompt lists')
+    for ds, anns in zip(data['data_samples'], prompt_anns):
+        ds.prompts = [GroundingPrompt(a['text'], a.get('tokens_positive'), a['gt_boxes'], a['gt_labels'],
+                                      *(a.get(k) for k in ('is_view_dep', 'is_hard', 'is_unique'))) for a in anns]
     return data
 
 

@@ -497,11 +497,35 @@ size_t es_attn_kv_bytes(int H, int Lk, int bf16);
 int es_attn_kv_prepare(const float* K, int ldk, const float* V, int ldv, int H, int Lk, int bf16, void* kv, void* stream);
 int es_attn_kv_fwd(const float* Q, int ldq, const void* kv, int H, int Lq, int Lk, float* O, int ldo, float* lse, int bf16,
                    void* stream);
-/* gradients of the same (recomputing the probabilities from lse); delta_scratch: B*H*Lq floats */
+/* Backward of a gather whose rows are shared between prompts (SparseFeatureFusion3DGrounder.loss_shared: the query rows of P
+ * prompts are gathered from ONE scene's L token rows; es_row_move mode 1 would race on rows several prompts selected).
+ * dy (P*Q, C), idx (P, Q) int32 rows of the scene, DISTINCT within one prompt (as es_topk_sorted writes them; an index outside
+ * [0, L) selects nothing).  dx (L, C): row l = sum of dy[p*Q + q] over the prompts p with idx[p][q] == l, formed in f32 from +0
+ * in ASCENDING p (rows nobody selected: +0); accumulate != 0: that sum is then added to what dx held.  No float atomics: the
+ * result is a function of the inputs alone.  workspace: es_rows_scatter_sum_workspace_ints(P, L) = P*L ints (the position table).
+ * Refusals, outputs untouched: -3 a leading dim below C, or not a multiple of 4 floats where rows are read as float4 (C % 4 == 0
+ * and 16-byte aligned dy / dx); -4 Q > L; -5 workspace too small. */
+size_t es_rows_scatter_sum_workspace_ints(int P, int L);
+int es_rows_scatter_sum(const float* dy, int ldy, const int* idx, int P, int Q, int L, int C, float* dx, int ldx, int accumulate,
+                        int* workspace, size_t workspace_ints, void* stream);
+/* gradients of es_attn_fwd (recomputing the probabilities from lse); delta_scratch: B*H*Lq floats */
 int es_attn_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
                 const float* dO, int ldd, const float* lse, int B, int H, int Lq, int Lk, const int* klen_dev,
                 float* delta_scratch, float* dQ, int ldgq, float* dK, int ldgk, float* dV, int ldgv, int accumulate, int bf16,
                 void* stream);
+/* Backward of es_attn_kv_fwd: Lq query rows (any number of prompts' queries) over ONE key / value set; the same function as es_attn_bwd
+ * with B = 1 and no key mask, with the same rounding points, built for a long Lq: Q * scale and dO are converted once per call into
+ * finished operand tiles in `workspace` (es_attn_kv_bwd_workspace_bytes(H, Lq, bf16) bytes, 16-byte aligned) which the dK / dV
+ * workgroups stream while their key tile stays resident (layout at the kernel, csrc/transformer.hip).  K / V: the f32 projections the
+ * operand image was prepared from; lse (H, Lq) as es_attn_kv_fwd stored it; delta_scratch: H*Lq floats.  dQ (Lq, H*32), dK / dV
+ * (Lk, H*32); accumulate != 0 adds to all three.  Deterministic: a (64-key tile, head) is owned by one workgroup that walks the query
+ * rows in ascending order; no float atomics.  -3: a leading dim that is not a multiple of 4 floats; -5: workspace missing, unaligned or
+ * too small (outputs untouched either way). */
+size_t es_attn_kv_bwd_workspace_bytes(int H, int Lq, int bf16);
+int es_attn_kv_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
+                   const float* dO, int ldd, const float* lse, int H, int Lq, int Lk, float* delta_scratch, void* workspace,
+                   size_t workspace_bytes, float* dQ, int ldgq, float* dK, int ldgk, float* dV, int ldgv, int accumulate, int bf16,
+                   void* stream);
 /* y = LayerNorm(x (+ res)) over the C columns of (n,C) rows (C <= 512); z = x + res is stored when z != NULL */
 int es_layernorm_fwd(const float* x, const float* res, int n, int C, const float* w, const float* b, float eps, float* y,
                      float* z, float* mean, float* rstd, void* stream);
