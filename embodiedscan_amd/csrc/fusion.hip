@@ -445,6 +445,71 @@ extern "C" int es_point_sample_prefix_fwd_pts(const int* coords, const float* po
   return 0;
 }
 
+// ---- Prefix fusion, one view at a time (walk sessions: EmbodiedOccPredictor.open_walk) --------------------------------------
+// The image volume of prefix t is the volume of prefix t - 1 with view t added, so a walk that receives its frames one by one keeps
+// only the running sum (n, C) and the valid-view count (n) and advances both by ONE view per call: no feature map of an earlier frame,
+// no limit on the number of calls.  Starting from sum = 0, nvalid = 0, the t-th call writes to `out` what k_point_sample_prefix_fwd
+// writes to rows [t n, (t + 1) n) on views 0 .. t, bit for bit: the same projection, the fetched row added in f32 whenever the view
+// has a pixel (not masked by validity), the same division.  Same shape as the siblings: one wave per voxel, 16 voxels per
+// workgroup, the meta block (32 + 16 floats: one view) staged in LDS when the workgroup's rows share a sample, lanes over channels.
+// Every lane projects the one view (a wave-uniform result), so there is no ballot and no per-view shuffle loop.
+__global__ __launch_bounds__(256) void k_point_sample_step_fwd(const int* __restrict__ coords, const float* __restrict__ pts, int n,
+                                                               const float* __restrict__ meta, int meta_stride,
+                                                               const float* __restrict__ feats, int Hf, int Wf, int C,
+                                                               float* __restrict__ sum, int* __restrict__ nval,
+                                                               float* __restrict__ out, int ldo, int* __restrict__ pix) {
+  __shared__ float metaS[ES_FUSE_PROJ + 16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * PS_PTS, i1 = min(n, i0 + PS_PTS);
+  const int b0 = coords[(size_t)i0 * 4], b1 = coords[(size_t)(i1 - 1) * 4];
+  const bool staged = (b0 == b1);                            // workgroup-uniform
+  if (staged)
+    for (int e = threadIdx.x; e < ES_FUSE_PROJ + 16; e += 256) metaS[e] = meta[(size_t)b0 * meta_stride + e];
+  __syncthreads();
+  const int MAXC = 8;                                   // supports C <= 512
+  for (int i = i0 + wv; i < i1; i += 4) {               // wave-uniform
+    int4 c = ((const int4*)coords)[i];
+    const float* m = staged ? metaS : meta + (size_t)c.x * meta_stride;
+    float x = pts[(size_t)i * 3], y = pts[(size_t)i * 3 + 1], z = pts[(size_t)i * 3 + 2];
+    undo_aug(m, x, y, z);
+    bool valid = false;
+    const int p = project_view(m, m + ES_FUSE_PROJ, x, y, z, Hf, Wf, valid);
+    int nvalid = 0;
+    if (lane == 0) {                                     // lane 0 alone reads and writes the count; the wave gets it by broadcast
+      nvalid = nval[i] + (valid ? 1 : 0);
+      nval[i] = nvalid;
+      pix[i] = p;
+    }
+    nvalid = __shfl(nvalid, 0, 64);
+    const float d = (float)max(nvalid, 1);
+    float* srow = sum + (size_t)i * C;
+    float* orow = out + (size_t)i * ldo;
+    const size_t off = (((size_t)c.x * Hf * Wf) + (size_t)max(p, 0)) * C;
+#pragma unroll
+    for (int q = 0; q < MAXC; ++q) {
+      int ch = lane + q * 64;
+      if (ch < C) {
+        float a = srow[ch];
+        if (p >= 0) {
+          a += feats[off + ch];
+          srow[ch] = a;
+        }
+        orow[ch] = nvalid > 0 ? __fdiv_rn(a, d) : 0.f;
+      }
+    }
+  }
+}
+extern "C" int es_point_sample_step_fwd_pts(const int* coords, const float* points, int n, const float* meta, int meta_stride,
+                                            const float* feats, int Hf, int Wf, int C, float* sum, int* nvalid, float* out, int ldo,
+                                            int* pix, void* stream) {
+  if (n <= 0) return 0;
+  if (C > 512) return -4;
+  hipLaunchKernelGGL(k_point_sample_step_fwd, dim3(es_cdiv(n, PS_PTS)), dim3(256), 0, (hipStream_t)stream, coords, points, n, meta,
+                     meta_stride, feats, Hf, Wf, C, sum, nvalid, out, ldo, pix);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // Backward of the prefix fusion.  View v of voxel i feeds every prefix t >= v, so the gradient that hit (i, v) carries to its
 // feature-map pixel is the SUFFIX sum g(i, v) = sum_{t = V-1 .. v, cnt[t][i] > 0} dout[t n + i] / cnt[t][i], taken from t = V - 1
 // downward.  The hit lists are those of es_point_sample_bwd (k_ps_link on the LAST prefix's counts: cnt[t][i] never falls with t,

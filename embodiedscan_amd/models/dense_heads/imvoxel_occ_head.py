@@ -39,6 +39,10 @@ class ImVoxelOccHead:
             logits, dims = self.forward(x[:1])[0]
         finally:
             E.TAPE.enabled = prev
+        return self.argmax(logits, dims)
+
+    def argmax(self, logits, dims):
+        """the prediction of one level's logits (n_vox, num_classes): (B, X, Y, Z) int64"""
         n = logits.d.shape[0]
         out = torch.empty(n, dtype=torch.int32, device=logits.d.device)
         call('es_row_argmax', P(logits.d), logits.d.shape[1], n, self.num_classes, P(out), hip.stream())

@@ -10,6 +10,23 @@ from ...parallel import BucketedGradReducer, is_dist
 from ...params import ParamArena
 
 
+class predict_guard:
+    """context: `det` in eval mode + tape off; the `training` flag and engine.TAPE.enabled are restored on exit.  A class of its own so
+    that detectors outside DetectorBase (the sparse fusion family) and the walk sessions share one copy"""
+
+    def __init__(self, det):
+        self.det = det
+
+    def __enter__(self):
+        self.was, self.prev = self.det.training, E.TAPE.enabled
+        self.det.train(False)
+        E.TAPE.enabled = False
+
+    def __exit__(self, *exc):
+        E.TAPE.enabled = self.prev
+        self.det.train(self.was)
+
+
 class DetectorBase:
     _version = 2
 
@@ -82,18 +99,7 @@ class DetectorBase:
 
     def _predict_guard(self):
         """context: eval mode + tape off"""
-        det = self
-
-        class _G:
-            def __enter__(self):
-                self.was, self.prev = det.training, E.TAPE.enabled
-                det.train(False)
-                E.TAPE.enabled = False
-
-            def __exit__(self, *exc):
-                E.TAPE.enabled = self.prev
-                det.train(self.was)
-        return _G()
+        return predict_guard(self)
 
     # data-parallel gradient buckets (parallel.BucketedGradReducer): name-prefix groups + the implicit last part; a
     # detector's forward records (tape index, part) pairs in `_tape_parts`: when the reverse replay of the tape has passed

@@ -24,6 +24,12 @@ from .sparse_featfusion_single_stage import SparseFeatureFusionSingleStage3DDete
 class Embodied3DDetector(SparseFeatureFusionSingleStage3DDetector):
     predict_chunk = 8
 
+    def open_walk(self, metainfo, max_frames=50):
+        """a session that takes the walk one frame at a time: walk.observe(img, points, depth2img) -> the detections of the prefix so
+        far (walk.py).  The feature maps of up to max_frames <= 64 frames stay on the device; ValueError above that"""
+        from .walk import DetWalk
+        return DetWalk(self, metainfo, max_frames)
+
     def _check(self, batch_inputs_dict, batch_data_samples):
         B, V = batch_inputs_dict['imgs'].shape[:2]
         T = len(batch_data_samples)

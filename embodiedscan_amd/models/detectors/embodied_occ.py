@@ -20,6 +20,12 @@ from .dense_fusion_occ import DenseFusionOccPredictor
 
 @MODELS.register_module()
 class EmbodiedOccPredictor(DenseFusionOccPredictor):
+    def open_walk(self, metainfo):
+        """a session that takes the walk one frame at a time: walk.observe(img, points, depth2img) -> the pred_occupancy of the prefix
+        so far (walk.py).  metainfo: what is constant over the walk -- image shape, augmentation keys, depth2img['origin']"""
+        from .walk import OccWalk
+        return OccWalk(self, metainfo)
+
     def extract_feat(self, batch_inputs_dict, batch_data_samples):
         """embodied_occ.py:118-247.  Returns [(Var (T*X_i*Y_i*Z_i, 128), (X_i, Y_i, Z_i))] fine -> coarse, prefix-major rows."""
         self._bind()

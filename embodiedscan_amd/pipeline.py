@@ -316,6 +316,22 @@ def make_cont_det_batch(dscan, visible=None):
     return data
 
 
+def walk_frames(dscan, n_rows=None):
+    """the frames of ONE sweeps scan as a walk session takes them (detector.open_walk): yields, per frame t, (t = its index into
+    dscan['img'], (r0, r1) = the rows of the un-projected cloud this frame adds, extrinsic, intrinsic).  r1 runs through
+    prefix_lengths, so the cloud after frame t is prefix t of make_cont_occ_batch / make_cont_det_batch.  n_rows None: the rows
+    depth_to_points makes (one per chosen pixel)."""
+    sl = dscan['points_slice_indices']
+    if n_rows is None:
+        n_rows = int(dscan['sel_pix'].numel()) if 'sel_pix' in dscan else int(sl[-1])
+    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(dscan['meta'].get(k), dict))
+    pm = dscan['meta'][key]
+    r0 = 0
+    for t, r1 in enumerate(prefix_lengths(sl, n_rows)):
+        yield t, (r0, max(r0, r1)), pm['extrinsic'][t], pm['intrinsic'][t]
+        r0 = max(r0, r1)
+
+
 def make_grounding_batch(dscans, anns=None):
     """`data` dict for SparseFeatureFusion3DGrounder.train_step: the detection batch with the prompt (`text`), the
     positive character spans (`tokens_positive`) and the TARGET boxes of the prompt as gt_instances_3d.

@@ -341,6 +341,13 @@ int es_point_sample_win_bwd(const int* coords, int n, int V, const int* win, con
 int es_point_sample_prefix_fwd_pts(const int* coords, const float* points, int n, const float* meta, int meta_stride, int V,
                                    const float* feats, int Hf, int Wf, int C, float* out, int ldo, int* pix, int* cnt,
                                    void* stream);
+/* the prefix fusion one view at a time (walk sessions): meta is an ES_FUSE_* block with ONE view (build_fusion_meta(..., n_views=1)),
+ * feats (B*Hf*Wf, C) this frame's map, sum (n, C) / nvalid (n) the state, read and written in place.  From sum = 0, nvalid = 0, after
+ * the t-th call with view t: out (n, C at row stride ldo) = rows [t*n, (t+1)*n) of es_point_sample_prefix_fwd_pts on views 0..t, bit
+ * for bit; nvalid = its cnt[t]; pix (n) = its column t.  No limit on the number of calls.  -4: C > 512 (nothing written). */
+int es_point_sample_step_fwd_pts(const int* coords, const float* points, int n, const float* meta, int meta_stride,
+                                 const float* feats, int Hf, int Wf, int C, float* sum, int* nvalid, float* out, int ldo,
+                                 int* pix, void* stream);
 /* its backward: dfeats pixel (v, p) (+)= sum over the voxels i that hit it, in ascending i, of
  * g(i, v) = sum_{t = V-1 .. v, cnt[t*n + i] > 0} dout[t*n + i] / cnt[t*n + i] (added from t = V - 1 downward).  Deterministic gather,
  * every pixel written; dout (V*n, ldo), scratch as es_point_sample_bwd. */
