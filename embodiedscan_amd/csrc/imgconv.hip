@@ -233,6 +233,7 @@ extern "C" int es_img_conv3_bf16(const void* X, int ldx, const void* W_bf16, int
   int wp, rows, bands;
   if (!img_conv_check(n_img, H, W, C, stride, mode, X, ldx, W_bf16, Y, y_half, ldy, wp, rows, bands)) return -4;
   if (mode == 1 && gate == nullptr) return -4;                 // (a missing operand, not a shape the query rejects)
+  if (mode == 0 && act != 0 && act != 1) return -4;            // (the epilogue here knows ReLU only: ELU (2) stays with the map kernels)
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* Wt = (const unsigned short*)W_bf16;
   const unsigned short* G = (const unsigned short*)gate;

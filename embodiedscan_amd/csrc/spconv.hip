@@ -670,6 +670,10 @@ __device__ __forceinline__ float4 bf16x4_to_f32(uint2 v) {
   return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
                      __uint_as_float(v.y & 0xffff0000u));
 }
+// activation of the fused epilogues: 1 ReLU, 2 ELU (expf(z) - 1.f below 0, the arithmetic of act_fwd in csrc/rowops.hip)
+__device__ __forceinline__ float ep_activate(float v, int act) {
+  return act == 2 ? (v > 0.f ? v : expf(v) - 1.f) : fmaxf(v, 0.f);
+}
 __device__ inline uint32_t pack_bf16(float a, float b) {
   f32x2_t x = {a, b};
   bf16x2_t y = __builtin_convertvector(x, bf16x2_t);
@@ -862,7 +866,7 @@ __global__ __launch_bounds__(256) void k_spconv_bf16(const float* __restrict__ X
             if (!(rv > 0.f)) v = 0.f;
           } else {
             if (ep_res) v += rv;
-            if (ep_act) v = fmaxf(v, 0.f);
+            if (ep_act) v = ep_activate(v, ep_act);
           }
           if (io & ES_IO_Y16) {                           // (Cout % 4 == 0: lanes li, li^1 are valid together) one 4-byte store per pair
             float vn = __shfl_xor(v, 1, 64);
@@ -1162,7 +1166,7 @@ __global__ __launch_bounds__(256, 3) void k_spconv_bf16_fast(const void* __restr
               if (!(rv > 0.f)) v = 0.f;
             } else {
               if (ep_res) v += rv;
-              if (ep_act) v = fmaxf(v, 0.f);
+              if (ep_act) v = ep_activate(v, ep_act);
             }
             if (io & ES_IO_Y16) {                         // bf16 activation rows: lanes (li, li^1) share one 4-byte store
               float vn = __shfl_xor(v, 1, 64);
@@ -1379,7 +1383,7 @@ __global__ __launch_bounds__(256, (KB == 1 && NBUF == 2) ? 3 : 2) void k_spconv_
               if (!(rv > 0.f)) v = 0.f;
             } else {
               if (ep_res) v += rv;
-              if (ep_act) v = fmaxf(v, 0.f);
+              if (ep_act) v = ep_activate(v, ep_act);
             }
             if (io & ES_IO_Y16) {
               float vn = __shfl_xor(v, 1, 64);
@@ -1538,7 +1542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
           if (!(r > 0.f)) x = 0.f;
         } else {
           if (ep_res) x += r;
-          if (ep_act) x = fmaxf(x, 0.f);
+          if (ep_act) x = ep_activate(x, ep_act);
         }
         return x;
       };
@@ -1739,7 +1743,7 @@ __global__ __launch_bounds__(256) void k_rowgemm2_bf16(const void* __restrict__ 
           if (!(q[e] > 0.f)) x = 0.f;
         } else {
           if (ep_res) x += q[e];
-          if (ep_act) x = fmaxf(x, 0.f);
+          if (ep_act) x = ep_activate(x, ep_act);
         }
         o[e] = x;
       }

@@ -171,6 +171,7 @@ size_t es_gen_transpose_wgrad_workspace_floats(const float* X, int ldx, const fl
 int es_set_option(int key, int value);
 /* Y = act((X*W) * scale[c] + shift[c] (+ res)): conv2d + frozen BatchNorm2d (+ residual) (+ ReLU) of mmdet.ResNet in one
  * launch (any shape; the tap-split of under-filled launches is not applied to fused calls).  act: 0 none, 1 ReLU,
+ * 2 ELU (expf(z) - 1 below 0, as es_affine_act_fwd),
  * 3 "gate": Y = (res > 0) ? (X*W) * scale[c] : 0 -- the data-gradient conv of layer i+1 fused with the ReLU / frozen-BN
  * backward of layer i (res = layer i's output, scale = its folded BN scale; shift may be NULL). */
 int es_spconv_fwd_bf16_affine(const void* X, int ldx, const void* W_bf16, const int* nbr, int n_out, int n_in, int K,
@@ -732,7 +733,7 @@ int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n
  * Bottleneck.conv2 (3x3, pad 1) of the w16 image backbone (mmdet.ResNet, mv-det3d_...py:24-34) fused with its frozen BatchNorm2d
  * (+ ReLU) -- what es_spconv_fwd_bf16_io does through es_image_map's 9-wide map -- on C -> C channels (C = 16 / 32 / 64):
  * mode 0 forward: X (n_img*H*W x ldx) bf16 rows on the INPUT grid, W_bf16 = the [9][Cout][Cin] copy, Y = act((X*W)*scale[c] +
- *   shift[c]) on the (H/stride, W/stride) output grid, bf16 rows (y_half 1) or f32; stride 1 or 2 (even H, W); act 0 / 1 (ReLU);
+ *   shift[c]) on the (H/stride, W/stride) output grid, bf16 rows (y_half 1) or f32; stride 1 or 2 (even H, W); act 0 / 1 (ReLU), any other act: -4 (ELU, 2, is the map kernels');
  * mode 1 gated data gradient of a stride-1 layer: X = f32 rows of the output gradient, W_bf16 = the natural [9][Cin][Cout] copy,
  *   gate (n_img*H*W x ldg) = the layer input's bf16 activation rows, Y (f32) = (gate > 0) ? (X * W^T, taps mirrored) * scale[c] : 0.
  * es_img_conv3_supported: 1 when the shape is taken (C = 16: output width <= 128, stride 1; 32: <= 64; 64: <= 32) with fresh contiguous
