@@ -259,3 +259,307 @@ extern "C" int es_img_conv3_bf16(const void* X, int ldx, const void* W_bf16, int
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------ stride-2 data gradients by address arithmetic
+// The data gradient of a stride-2 layer through the inverse map is mostly work on absent taps: a pixel (y, x) of the input grid receives
+// from tap (ky, kx) only where y + 1 - ky and x + 1 - kx are even -- 1, 2, 2 or 4 of the nine taps by the parity of (y, x) -- and a 128-row
+// tile of the map kernels holds every parity, so it runs all nine taps on every row (zero rows for the absent ones); the 1x1 / stride-2
+// layers multiply and store four rows for every one that has a source.  Here the address arithmetic names the present taps:
+//   k_img_dgrad3_s2  gated data gradient of a 3x3 / stride-2 / pad-1 layer: dX = (A > 0) ? (sum_taps G[o(p, tap)] W[tap]^T) * scale[c] : 0.
+//     A workgroup owns a band of 2-row cells of ONE image; the gradient rows (f32 -> bf16 on the way in) sit in a 4-slot LDS ring of
+//     Wo + 1 pixels whose pad pixel stays zero; cell cy needs gradient rows cy (input row 2 cy: ky = 1; row 2 cy + 1: ky = 2) and cy + 1
+//     (row 2 cy + 1: ky = 0).  Per 16-pixel block of one x parity only the taps of that (y, x) parity class are issued, in ascending tap
+//     order and 32-channel chunks with v_mfma_f32_16x16x32_bf16: the order of the map kernels, whose skipped taps added exact zeros --
+//     bit-identical.  Weights ([9][Cin][Cout] natural copy) in registers, waves split as in k_img_conv3.
+//   k_img_dgrad1_s2  data gradient of a 1x1 / stride-2 layer: a row GEMM over the (H/2 x W/2) gradient rows only, stored to pixel
+//     (2 oy, 2 ox); accumulate = 0: the workgroup also stores zeros (16-byte stores) to the other three pixels of the 2x2 cell.
+template <int C, int WPO>
+__global__ __launch_bounds__(256) void k_img_dgrad3_s2(const float* __restrict__ G, int ldg, const unsigned short* __restrict__ Wn,
+                                                       const float* __restrict__ scale, const unsigned short* __restrict__ gate, int lda,
+                                                       float* __restrict__ dX, int ldx, int H, int W, int cells_per_wg, int bands) {
+  constexpr int RB = C * 2;                                 // bytes per pixel row of the ring
+  constexpr int XP = WPO + 1, X_BYTES = XP * RB;            // (pixel WPO: the zero pad read by the last odd pixel's kx = 0 tap)
+  constexpr int NS = 4;
+  constexpr int NCB = C / 16;
+  constexpr bool CO_SPLIT = NCB >= 4;
+  constexpr int CBW = CO_SPLIT ? NCB / 4 : NCB;
+  constexpr int KS = C / 32;
+  constexpr int NPB = WPO / 16;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[NS * X_BYTES];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 15, kq = lane >> 4;
+  const int im = blockIdx.x / bands, band = blockIdx.x - im * bands;
+  const int Ho = H / 2, Wo = W / 2;
+  const int c0 = band * cells_per_wg, c1 = min(Ho, c0 + cells_per_wg);
+  if (c0 >= c1) return;
+  for (int i = t; i < NS * X_BYTES / 16; i += 256) ((uint4*)smem)[i] = make_uint4(0u, 0u, 0u, 0u);
+
+  // weights -> registers: tap k of the natural [tap][Cin][Cout] copy read as [N = Cin][K = Cout]
+  bf16x8_t Bf[9][KS][CBW];
+#pragma unroll
+  for (int k = 0; k < 9; ++k)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int cw = 0; cw < CBW; ++cw) {
+        const int cb = CO_SPLIT ? wv * CBW + cw : cw;
+        const uint4 v = *(const uint4*)(Wn + ((size_t)k * C + cb * 16 + li) * C + ks * 32 + kq * 8);
+        Bf[k][ks][cw] = __builtin_bit_cast(bf16x8_t, v);
+      }
+  __syncthreads();                                            // the ring is zero
+
+  constexpr int NLG = (WPO * C / 4 + 255) / 256;
+  float4 greg[NLG];
+  auto load_g = [&](int oy) {
+    const float* src = G + ((size_t)im * Ho + oy) * Wo * ldg;
+#pragma unroll
+    for (int j = 0; j < NLG; ++j) {
+      const int e = j * 256 + t, px = e / (C / 4), c4 = e - px * (C / 4);
+      greg[j] = (oy < Ho && px < Wo) ? *(const float4*)(src + (size_t)px * ldg + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto store_g = [&](int oy) {
+    if (oy >= Ho) return;                                     // (a row outside the image: its reads are zeroed below)
+    unsigned char* dst = smem + (oy & (NS - 1)) * X_BYTES;
+#pragma unroll
+    for (int j = 0; j < NLG; ++j) {
+      const int e = j * 256 + t, px = e / (C / 4), c4 = e - px * (C / 4);
+      if (px < WPO) {
+        uint2 v;
+        v.x = es_pack_bf16(greg[j].x, greg[j].y);
+        v.y = es_pack_bf16(greg[j].z, greg[j].w);
+        *(uint2*)(dst + px * RB + c4 * 8) = v;
+      }
+    }
+  };
+
+  load_g(c0);
+  store_g(c0);
+  load_g(c0 + 1);
+  for (int cy = c0; cy < c1; ++cy) {
+    store_g(cy + 1);                                          // (its slot held row cy - 3: nobody reads it any more)
+    __syncthreads();                                          // rows cy, cy + 1 are in the ring; cell cy - 1 has been consumed
+    load_g(cy + 2);
+#pragma unroll 1
+    for (int pb = CO_SPLIT ? 0 : wv; pb < NPB; pb += CO_SPLIT ? 1 : 4) {
+      const int q0 = pb * 16;
+      if (q0 >= Wo) break;
+#pragma unroll
+      for (int cls = 0; cls < 4; ++cls) {                    // the four parity classes of the cell: (row 2 cy + yr, pixels 2 q + px)
+        const int yr = cls >> 1, px = cls & 1;
+        f32x4 acc[CBW];
+#pragma unroll
+        for (int cw = 0; cw < CBW; ++cw) acc[cw] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          if ((ky == 1) != (yr == 0)) continue;              // even rows: ky = 1; odd rows: ky = 0, 2
+          const int oy = (yr == 1 && ky == 0) ? cy + 1 : cy;
+          const bool rowok = oy < Ho;                        // (the last odd row has no ky = 0 tap: the slot may hold another row)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            if ((kx == 1) != (px == 0)) continue;            // even pixels: kx = 1; odd pixels: kx = 0, 2
+            const int k = ky * 3 + kx;
+            const int ox = q0 + li + ((px == 1 && kx == 0) ? 1 : 0);
+            const unsigned char* xr = smem + (oy & (NS - 1)) * X_BYTES + ox * RB;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+              uint4 av = *(const uint4*)(xr + (ks * 32 + kq * 8) * 2);
+              if (!rowok) av = make_uint4(0u, 0u, 0u, 0u);
+              const bf16x8_t a = __builtin_bit_cast(bf16x8_t, av);
+#pragma unroll
+              for (int cw = 0; cw < CBW; ++cw) acc[cw] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, Bf[k][ks][cw], acc[cw], 0, 0, 0);
+            }
+          }
+        }
+        // epilogue of the map kernels' gated launch: lane (li, kq) holds pixels 2 (q0 + kq * 4 + r) + px of channel cb * 16 + li
+        const size_t rowy = ((size_t)im * H + 2 * cy + yr) * W;
+#pragma unroll
+        for (int cw = 0; cw < CBW; ++cw) {
+          const int col = (CO_SPLIT ? wv * CBW + cw : cw) * 16 + li;
+          const float sc = scale ? scale[col] : 1.f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int q = q0 + kq * 4 + r;
+            if (q < Wo) {
+              const size_t row = rowy + 2 * q + px;
+              const float v = (acc[cw][r] + 0.f) * sc + 0.f;
+              const float gt = __uint_as_float((uint32_t)gate[row * lda + col] << 16);
+              dX[row * ldx + col] = gt > 0.f ? v : 0.f;
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+#define ES_S2_LD 48                                         // bf16 elements per padded LDS row (96 B, as HLD of spconv.hip)
+template <int NT>
+__global__ __launch_bounds__(256) void k_img_dgrad1_s2(const float* __restrict__ G, int ldg, const unsigned short* __restrict__ Wn, int n_g,
+                                                       int Kred, int Wo, float* __restrict__ dX, int ldx, int accumulate) {
+  constexpr int NF = NT / 16;
+  constexpr int NB = (NT + 63) / 64;
+  constexpr int LD = ES_S2_LD;
+  __shared__ __attribute__((aligned(16))) unsigned short As[2 * 128 * LD];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2 * NT * LD];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 15, kq = lane >> 4;
+  const int row0 = blockIdx.x * 128, n0 = blockIdx.y * NT;
+  // gradient row (im, oy, ox) = q * Wo + ox with q = im * Ho + oy  ->  pixel (2 oy, 2 ox) of the input grid = row 4 q Wo + 2 ox
+  if (!accumulate) {                                          // the three pixels of the 2x2 cell that have no source
+    constexpr int C4 = NT / 4;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = t; e < 128 * C4; e += 256) {
+      const int r = e / C4, c4 = e - r * C4, row = row0 + r;
+      if (row < n_g) {
+        const int q = row / Wo, ox = row - q * Wo;
+        float* p = dX + ((size_t)4 * q * Wo + 2 * ox) * ldx + n0 + c4 * 4;
+        *(float4*)(p + ldx) = z;
+        *(float4*)(p + (size_t)2 * Wo * ldx) = z;
+        *(float4*)(p + ((size_t)2 * Wo + 1) * ldx) = z;
+      }
+    }
+  }
+  f32x4 acc[2][NF];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < NF; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int nC = Kred / 32;
+  const int a_r = t >> 1, a_kk = (t & 1) * 16;               // A: one row, 16 consecutive channels
+  const int b_n = t >> 2, b_kk = (t & 3) * 8;                // B: output channel b_n (+ 64), 8 consecutive reduction elements
+  const int b_w = ((NT % 64 == 0) || b_n < NT) ? b_n : 0;    // (NT = 32: the upper threads re-read column 0 and store nothing)
+  const bool a_ok = row0 + a_r < n_g;
+  const float* a_src = G + (size_t)(a_ok ? row0 + a_r : 0) * ldg + a_kk;
+  struct Regs { float4 a[4]; uint4 b[NB]; };
+  auto load_chunk = [&](Regs& R, int c) {
+    const float4* pa = (const float4*)(a_src + c * 32);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) R.a[q] = pa[q];
+#pragma unroll
+    for (int h = 0; h < NB; ++h) R.b[h] = *(const uint4*)(Wn + (size_t)(n0 + b_w + h * 64) * Kred + c * 32 + b_kk);
+  };
+  auto store_chunk = [&](const Regs& R, int buf) {
+    uint4 v0 = make_uint4(es_pack_bf16(R.a[0].x, R.a[0].y), es_pack_bf16(R.a[0].z, R.a[0].w), es_pack_bf16(R.a[1].x, R.a[1].y),
+                          es_pack_bf16(R.a[1].z, R.a[1].w));
+    uint4 v1 = make_uint4(es_pack_bf16(R.a[2].x, R.a[2].y), es_pack_bf16(R.a[2].z, R.a[2].w), es_pack_bf16(R.a[3].x, R.a[3].y),
+                          es_pack_bf16(R.a[3].z, R.a[3].w));
+    if (!a_ok) v0 = v1 = make_uint4(0u, 0u, 0u, 0u);
+    uint4* pa = (uint4*)&As[buf * 128 * LD + a_r * LD + a_kk];
+    pa[0] = v0;
+    pa[1] = v1;
+#pragma unroll
+    for (int h = 0; h < NB; ++h)
+      if ((NT % 64 == 0) || b_n < NT) *(uint4*)&Bs[buf * NT * LD + (b_n + h * 64) * LD + b_kk] = R.b[h];
+  };
+  auto compute = [&](int buf) {
+    bf16x8_t a[2], b[NF];
+#pragma unroll
+    for (int mf = 0; mf < 2; ++mf) a[mf] = *(const bf16x8_t*)&As[buf * 128 * LD + (wv * 32 + mf * 16 + li) * LD + kq * 8];
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf) b[nf] = *(const bf16x8_t*)&Bs[buf * NT * LD + (nf * 16 + li) * LD + kq * 8];
+#pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mf], b[nf], acc[mf][nf], 0, 0, 0);
+  };
+  // chunk c is computed from buffer c & 1 while chunk c + 1 is written to the other one and chunk c + 2 is in flight: one barrier per chunk
+  Regs R;
+  load_chunk(R, 0);
+  store_chunk(R, 0);
+  load_chunk(R, nC > 1 ? 1 : 0);
+  __syncthreads();
+  for (int c = 0; c < nC; ++c) {
+    if (c + 1 < nC) store_chunk(R, (c + 1) & 1);
+    load_chunk(R, c + 2 < nC ? c + 2 : c);                    // (unconditional: past the end it re-reads a chunk that is never stored)
+    compute(c & 1);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = row0 + wv * 32 + mf * 16 + kq * 4 + r;
+        if (row < n_g) {
+          const int q = row / Wo, ox = row - q * Wo;
+          float* p = dX + ((size_t)4 * q * Wo + 2 * ox) * ldx + n0 + nf * 16 + li;
+          const float v = acc[mf][nf][r] + 0.f;               // (the map kernels' `+ bias`, absent: -0 -> +0)
+          *p = accumulate ? (*p + v) : v;
+        }
+      }
+}
+
+static int ES_OPT_IMG_S2 = 1;
+static int ES_OPT_IMG_S2_WGS = 2048;     // (A/B on 80 images, profiles/img_strided_dgrad_ab.txt: 32 channels 99 us at 1 024, 90 at 2 048; 64 channels 84 / 67)
+extern "C" int es_img_stride_set_option(int key, int value) {
+  if (key == 52) { ES_OPT_IMG_S2 = value; return 0; }
+  if (key == 53) { ES_OPT_IMG_S2_WGS = value; return 0; }
+  return -1;
+}
+
+// C = 32 (gradient width <= 64) and C = 64 (<= 32): the register-resident weights of k_img_conv3.  C = 128 (layer4.0.conv2, 30 -> 15) is not
+// built: 9 x 128 x 128 bf16 does not fit in registers; it stays on the map kernel (below the 71 us cut of profiles/r6j_slowest_launches.txt).
+static bool img_dgrad3_s2_check(int n_img, int H, int W, int C, const void* G, int ldg, const void* Wn, const void* gate, int lda,
+                                const void* dX, int ldx, int& cells, int& bands) {
+  if (!ES_OPT_IMG_S2 || n_img <= 0 || H <= 0 || W <= 0 || (H % 2) || (W % 2)) return false;
+  const int Ho = H / 2, Wo = W / 2;
+  if (!((C == 32 && Wo <= 64) || (C == 64 && Wo <= 32))) return false;
+  if ((ldg % 4) || (ldx % 4) || ldg < C || ldx < C || lda < C) return false;
+  if ((((uintptr_t)G) | ((uintptr_t)Wn) | ((uintptr_t)dX)) & 15) return false;
+  const int ldm = ldx > lda ? ldx : lda;
+  if ((long long)n_img * H * W * ldm >= (1ll << 31) || (long long)n_img * Ho * Wo * ldg >= (1ll << 31)) return false;
+  bands = ES_OPT_IMG_S2_WGS / n_img;
+  if (bands < 1) bands = 1;
+  if (bands > Ho) bands = Ho;
+  cells = es_cdiv(Ho, bands);
+  bands = es_cdiv(Ho, cells);
+  return true;
+}
+
+extern "C" int es_img_dgrad3_s2_supported(int n_img, int H, int W, int C) {
+  int cells, bands;
+  return img_dgrad3_s2_check(n_img, H, W, C, nullptr, C, nullptr, nullptr, C, nullptr, C, cells, bands) ? 1 : 0;
+}
+
+extern "C" int es_img_dgrad3_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int C, const float* scale,
+                                     const void* gate, int lda, float* dX, int ldx, void* stream) {
+  int cells, bands;
+  if (!img_dgrad3_s2_check(n_img, H, W, C, G, ldg, Wn_bf16, gate, lda, dX, ldx, cells, bands)) return -4;
+  if (G == nullptr || Wn_bf16 == nullptr || gate == nullptr || dX == nullptr) return -4;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* Wn = (const unsigned short*)Wn_bf16;
+  const unsigned short* A = (const unsigned short*)gate;
+  if (C == 32)
+    hipLaunchKernelGGL((k_img_dgrad3_s2<32, 64>), dim3(n_img * bands), dim3(256), 0, st, G, ldg, Wn, scale, A, lda, dX, ldx, H, W, cells, bands);
+  else
+    hipLaunchKernelGGL((k_img_dgrad3_s2<64, 32>), dim3(n_img * bands), dim3(256), 0, st, G, ldg, Wn, scale, A, lda, dX, ldx, H, W, cells, bands);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool img_dgrad1_s2_check(int n_img, int H, int W, int Cg, int Cx, const void* G, int ldg, const void* Wn, const void* dX, int ldx) {
+  if (!ES_OPT_IMG_S2 || n_img <= 0 || H <= 0 || W <= 0 || (H % 2) || (W % 2)) return false;
+  if (Cg <= 0 || Cx <= 0 || (Cg % 32) || (Cx % 32)) return false;
+  if ((ldg % 4) || (ldx % 4) || ldg < Cg || ldx < Cx) return false;
+  if ((((uintptr_t)G) | ((uintptr_t)Wn) | ((uintptr_t)dX)) & 15) return false;
+  return (long long)n_img * H * W * ldx < (1ll << 31) && (long long)n_img * (H / 2) * (W / 2) * ldg < (1ll << 31);
+}
+
+extern "C" int es_img_dgrad1_s2_supported(int n_img, int H, int W, int Cg, int Cx) {
+  return img_dgrad1_s2_check(n_img, H, W, Cg, Cx, nullptr, Cg, nullptr, nullptr, Cx) ? 1 : 0;
+}
+
+extern "C" int es_img_dgrad1_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int Cg, int Cx, float* dX, int ldx,
+                                     int accumulate, void* stream) {
+  if (!img_dgrad1_s2_check(n_img, H, W, Cg, Cx, G, ldg, Wn_bf16, dX, ldx)) return -4;
+  if (G == nullptr || Wn_bf16 == nullptr || dX == nullptr) return -4;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* Wn = (const unsigned short*)Wn_bf16;
+  const int n_g = n_img * (H / 2) * (W / 2), Wo = W / 2;
+  if (Cx % 128 == 0)
+    hipLaunchKernelGGL((k_img_dgrad1_s2<128>), dim3(es_cdiv(n_g, 128), Cx / 128), dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+  else
+    hipLaunchKernelGGL((k_img_dgrad1_s2<32>), dim3(es_cdiv(n_g, 128), Cx / 32), dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

@@ -420,6 +420,9 @@ def _wgrad(name, sw, dW, *args, like=None, acc=None):
 
 
 IMG_WGRAD = [os.environ.get('ES_IMG_WGRAD', '1') != '0']     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
+# stride-2 data gradients of the image backbone by address arithmetic (csrc/imgconv.hip: es_img_dgrad3_s2_bf16 / es_img_dgrad1_s2_bf16),
+# bit-identical to the map-kernel launches they replace (A/B switch and the way back)
+IMG_STRIDED_DGRAD = [os.environ.get('ES_IMG_STRIDED_DGRAD', '1') != '0']
 # FCAF3D head backward without the work its result does not need (A/B switch; off: exactly the launches before it existed): the 8 taps of a
 # generative transposed convolution's weight gradient in one launch (es_gen_transpose_wgrad_bf16), the head gradient matrix cleared by the
 # focal-loss launch instead of a zero fill (es_focal_loss_clear, models/dense_heads/fcaf3d_head.py)
@@ -844,6 +847,12 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
                 and hip.try_call('es_img_conv3_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, 1, 1, P(gate), 0, P(x.d),
                                  _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)):
             return
+        # 3x3 / stride-2 image layer: only the taps of each pixel's parity class (csrc/imgconv.hip, k_img_dgrad3_s2)
+        if (IMG_STRIDED_DGRAD[0] and img is not None and K == 9 and img[3] == 2 and cin == cout and x.d.dtype == torch.bfloat16
+                and gy.dtype == torch.float32 and hip.raw('es_img_dgrad3_s2_supported')(img[0], img[1], img[2], cin) == 1
+                and hip.try_call('es_img_dgrad3_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, P(gate), P(x.d),
+                                 _ld(x.d), P(x.g), _ld(x.g), s)):
+            return
         if x.d.dtype == torch.bfloat16:          # the gate operand is the bf16 activation (only its sign is read)
             call('es_spconv_fwd_bf16_io', P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
                  P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
@@ -852,6 +861,12 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
                  P(x.d), _ld(x.d), 3, P(x.g), _ld(x.g), s)
         return
     g, acc = _grad_target(x, x.d)
+    # 1x1 / stride-2 image layer (downsample.0): a row GEMM over the gradient rows only, stored to the even pixels (k_img_dgrad1_s2)
+    if (IMG_STRIDED_DGRAD[0] and img is not None and K == 1 and img[3] == 2 and bf and gh is None and dn_d is None
+            and gy.dtype == torch.float32 and g.dtype == torch.float32 and n_in == img[0] * img[1] * img[2]
+            and hip.raw('es_img_dgrad1_s2_supported')(img[0], img[1], img[2], cout, cin) == 1
+            and hip.try_call('es_img_dgrad1_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cout, cin, P(g), _ld(g), acc, s)):
+        return
     if dn_d is not None:                         # dense engine (dense_ok)
         if _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(g), _ld(g), acc, gh):
             return
@@ -874,8 +889,8 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
     sole_consumer: promise that x feeds nothing but this conv; if x itself came out of a fused conv+BN+ReLU, its
     ReLU/BN backward is then folded into this conv's data-gradient launch.
     out_bf16: store the output rows in bf16 (the image backbone's activations); x / res may themselves be bf16 row matrices.
-    img: (n_img, H, W, stride) when the map is a 3x3 / pad 1 image-grid map: the weight gradient may then run by address arithmetic
-    (csrc/imgwgrad.hip) instead of through the map."""
+    img: (n_img, H, W, stride) when the map is a 3x3 / pad 1 (or 1x1 / pad 0) image-grid map: the weight gradient (csrc/imgwgrad.hip) and
+    the data gradient (csrc/imgconv.hip) may then run by address arithmetic instead of through the map."""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
     if PRECISION[0] != 'bf16':

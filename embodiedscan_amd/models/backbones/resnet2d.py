@@ -177,7 +177,7 @@ class ResNet:
                     else:
                         dn, di, _, _, _ = g_in.conv_map(1, stride, 0)
                         idt = E.conv_affine(cur, self._par(p + 'downsample.0.weight'), dn, di, n_out,
-                                            *self.fold[p + 'downsample.1'], act=0, out_bf16=a16)
+                                            *self.fold[p + 'downsample.1'], act=0, out_bf16=a16, img=(n_img, g_in.H, g_in.W, stride))
                 else:
                     idt = cur
                 cur = E.conv_affine(o, self._par(p + 'conv3.weight'), None, None, n_out, *self.fold[p + 'bn3'], act=1,

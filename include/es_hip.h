@@ -745,6 +745,28 @@ int es_img_conv3_bf16(const void* X, int ldx, const void* W_bf16, int n_img, int
                       void* stream);
 int es_img_conv_set_option(int key, int value);
 
+/* ---- stride-2 data gradients of the image backbone by address arithmetic (csrc/imgconv.hip) -------------------------------
+ * (H, W) = the layer's INPUT grid (both even), the gradient G lives on the (H/2, W/2) grid; f32 gradient rows are rounded to bf16 on the way
+ * in, f32 accumulation, taps and 32-channel chunks in the map kernels' order: bit-identical to the launches they replace.
+ * es_img_dgrad3_s2_bf16: gated data gradient of a 3x3 / stride-2 / pad-1 layer on C -> C channels -- es_spconv_fwd_bf16_io with act 3 on
+ *   es_inverse_map(es_image_map(3, 3, 2, 1)): dX (n_img*H*W x ldx, f32) = (gate > 0) ? (sum_taps G[o(p, tap)] . W[tap]^T) * scale[c] : 0 with
+ *   G (n_img*H/2*W/2 x ldg) f32 rows, W_bf16 = the natural [9][Cin][Cout] copy, gate (n_img*H*W x lda) = the layer input's bf16 activation
+ *   rows.  Only the 1, 2, 2 or 4 taps that exist for the parity of (y, x) are issued.  Takes C = 32 with W <= 128 and C = 64 with W <= 64.
+ * es_img_dgrad1_s2_bf16: data gradient of a 1x1 / stride-2 layer -- es_spconv_fwd_bf16 on the 1-wide inverse map:
+ *   dX[(im, 2 oy, 2 ox)] (+)= G[(im, oy, ox)] . W^T, G (x ldg) f32 rows of Cg channels, W_bf16 = the natural [Cx][Cg] copy, dX (x ldx) f32 rows
+ *   of Cx channels; Cg, Cx multiples of 32.  accumulate 0: the same launch stores zeros to the three other pixels of every 2x2 cell;
+ *   accumulate 1: they are not touched.
+ * The _supported queries answer for fresh contiguous operands; the launchers apply the same check (even H / W, leading dimensions multiples
+ * of 4, 16-byte aligned pointers, rows x ld < 2^31) to the operands they are given and return -4, writing nothing, where it fails.
+ * es_img_stride_set_option: 52 on / off, 53 workgroups aimed for by the 3x3 kernel. */
+int es_img_dgrad3_s2_supported(int n_img, int H, int W, int C);
+int es_img_dgrad3_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int C, const float* scale,
+                          const void* gate, int lda, float* dX, int ldx, void* stream);
+int es_img_dgrad1_s2_supported(int n_img, int H, int W, int Cg, int Cx);
+int es_img_dgrad1_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int Cg, int Cx, float* dX, int ldx,
+                          int accumulate, void* stream);
+int es_img_stride_set_option(int key, int value);
+
 #ifdef __cplusplus
 }
 #endif
