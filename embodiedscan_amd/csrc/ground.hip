@@ -115,6 +115,128 @@ extern "C" int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int
   return 0;
 }
 
+// ------------------------------------------------------------------ scene inventory filter (demo/demo.py:84-130, nms_filter)
+// The demo's object list: walk the rows by descending score (order = es_topk_sorted: ties to the lower row); skip a row whose class
+// already holds topk_per_class kept rows, whose score is below score_thr, or whose 9-DoF IoU with ANY kept row (whatever its class)
+// exceeds iou_thr; keep the others.  The reference builds the whole n x n matrix and loops on the host; here the greedy is
+// sequential in the KEPT rows only: one workgroup holds a dead flag per sorted position and the class counters in LDS, and every
+// kept row costs one pass over the later positions that are still alive -- iou(candidate, kept), the candidate as the first
+// (inclusive) argument, rounded to f32 and compared in f32: the [candidate][kept] element es_box3d_iou stores.  A NaN IoU (a
+// zero-volume pair) compares false and does not suppress.  Rows below the score threshold (a suffix after the sort), rows with a
+// label outside [0, n_classes) and order entries outside [0, n) are dead from the start; m bounds the live positions.  A class's
+// counter only grows, so a row met over quota is dead for good -- it never suppresses anything, exactly as in the reference.
+// A pass has two phases.  One clipping takes a wave about 0.2 ms (f64, two 16-vertex polygons per lane in scratch), and a wave
+// waits for its slowest lane, so lanes that walk their share of the positions and clip where they must make the pass as long as
+// the number of loop trips in which SOME lane clips.  Phase 1 therefore only restates box_iou3d's bounding-sphere test -- the same
+// f64 expressions on the same values, no FMA contraction in this file, so it rejects exactly the pairs box_iou3d returns 0.0 for --
+// and collects the surviving positions in an LDS list (in arrival order: every entry is judged on its own, so the order does not
+// reach the result); phase 2 deals the list out one entry per lane.
+#define FILT_MAX 16384             // rows: what es_topk_sorted orders
+#define FILT_MAX_CLS 4096
+#define FILT_T 256
+// the bounding-sphere radius as box_iou3d forms it: half sizes b[3..5] * 0.5, sqrt of the sum of their squares in that order
+__device__ inline double filt_radius(const double* b) {
+  const double h0 = b[3] * 0.5, h1 = b[4] * 0.5, h2 = b[5] * 0.5;
+  return sqrt(h0 * h0 + h1 * h1 + h2 * h2);
+}
+__global__ __launch_bounds__(FILT_T) void k_box3d_iou_filter(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                             const int* __restrict__ labels, const int* __restrict__ order, int n,
+                                                             int n_classes, float iou_thr, float score_thr, int topk,
+                                                             int* __restrict__ keep_idx, int* __restrict__ keep_cnt) {
+  __shared__ unsigned char s_dead[FILT_MAX];
+  __shared__ unsigned short s_list[FILT_MAX];      // positions whose sphere meets the kept row's (a position is < 16384)
+  __shared__ unsigned short s_cnt[FILT_MAX_CLS];   // kept rows per class (<= n <= 16384)
+  __shared__ int s_first[FILT_T / 64];
+  __shared__ int s_m, s_nlist;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int c = tid; c < n_classes; c += FILT_T) s_cnt[c] = 0;
+  if (tid == 0) s_m = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int p = tid; p < n; p += FILT_T) {
+    const int r = order[p];
+    bool live = r >= 0 && r < n;
+    if (live) {
+      const int l = labels[r];
+      live = l >= 0 && l < n_classes && !(scores[r] < score_thr);
+    }
+    s_dead[p] = live ? 0 : 1;
+    if (live) mine = p + 1;
+  }
+  if (mine) atomicMax(&s_m, mine);
+  __syncthreads();
+  const int m = s_m;                       // one past the last live position
+  int nk = 0, cur = 0;
+  while (true) {
+    // the first live position at or after `cur` whose class has room (the same value in every lane)
+    int found = -1;
+    for (int base = cur; base < m; base += FILT_T) {
+      const int p = base + tid;
+      bool ok = false;
+      if (p < m && !s_dead[p]) {
+        if ((int)s_cnt[labels[order[p]]] < topk) ok = true;
+        else s_dead[p] = 1;
+      }
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0) s_first[w] = bal ? base + w * 64 + __ffsll(bal) - 1 : 0x7fffffff;
+      __syncthreads();
+      int f = s_first[0];
+#pragma unroll
+      for (int k = 1; k < FILT_T / 64; ++k) f = min(f, s_first[k]);
+      __syncthreads();                     // every lane has read s_first before the next chunk rewrites it
+      if (f != 0x7fffffff) { found = f; break; }
+    }
+    if (found < 0) break;
+    const int rk = order[found];
+    if (tid == 0) { keep_idx[nk] = rk; s_cnt[labels[rk]] += 1; s_nlist = 0; }
+    ++nk;
+    __syncthreads();
+    double kb[9], a[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) kb[c] = boxes[(size_t)rk * 9 + c];
+    const V3 kc = v3(kb[0], kb[1], kb[2]);
+    const double kr = filt_radius(kb);
+    for (int p = found + 1 + tid; p < m; p += FILT_T) {
+      if (s_dead[p]) continue;
+      const int r = order[p];
+      const V3 d = v3((double)boxes[(size_t)r * 9], (double)boxes[(size_t)r * 9 + 1], (double)boxes[(size_t)r * 9 + 2]) - kc;
+      a[3] = boxes[(size_t)r * 9 + 3]; a[4] = boxes[(size_t)r * 9 + 4]; a[5] = boxes[(size_t)r * 9 + 5];
+      const double rs = filt_radius(a) + kr;
+      if (dot3(d, d) > rs * rs) {          // box_iou3d returns 0.0 here
+        if (0.0f > iou_thr) s_dead[p] = 1;
+      } else {
+        s_list[atomicAdd(&s_nlist, 1)] = (unsigned short)p;
+      }
+    }
+    __syncthreads();
+    const int nl = s_nlist;
+    for (int i = tid; i < nl; i += FILT_T) {
+      const int p = s_list[i];
+      const int r = order[p];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) a[c] = boxes[(size_t)r * 9 + c];
+      if ((float)box_iou3d(a, kb) > iou_thr) s_dead[p] = 1;
+    }
+    cur = found + 1;
+    __syncthreads();                       // the flags, the counter and the list of this pass are settled before the next search
+  }
+  if (tid == 0) keep_cnt[0] = nk;
+}
+extern "C" int es_box3d_iou_filter(const float* boxes, const float* scores, const int* labels, const int* order, int n, int n_classes,
+                                   float iou_thr, float score_thr, int topk_per_class, int* keep_idx, int* keep_cnt, void* stream) {
+  if (n > FILT_MAX || n_classes < 1 || n_classes > FILT_MAX_CLS || topk_per_class < 1) return -4;
+  if (n < 0) return -5;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    ES_TRY(hipMemsetAsync(keep_cnt, 0, sizeof(int), st));
+    return 0;
+  }
+  hipLaunchKernelGGL(k_box3d_iou_filter, dim3(1), dim3(FILT_T), 0, st, boxes, scores, labels, order, n, n_classes, iou_thr, score_thr,
+                     topk_per_class, keep_idx, keep_cnt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ detection metric (IndoorDetMetric, eval/indoor_eval.py)
 // eval_det_cls:111-132,145-158: one lane per prediction walks the ground-truth boxes of its (scene, class) group in the scene's
 // order.  A prediction with a face below 2e-4 m^2 (f32 products) has its three sizes clamped to 2e-2 first; the IoU is the f64

@@ -1,0 +1,282 @@
+"""A posed RGB-D recording in, an object list (or an occupancy volume) out: the reference's demo (demo/demo.py) without the rendering.
+
+    python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json]
+
+reads D/S/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}, runs the model of CONFIG in
+`predict` mode (or frame by frame through a walk session with --walk) and writes the filtered boxes, scores, labels and class names
+(occupancy models: the volume's shape and class histogram) as JSON.
+
+filter_instances is the demo's nms_filter (demo.py:84-130) on the device: a score threshold, CLASS-AGNOSTIC greedy suppression on the
+true 9-DoF IoU and a per-class quota, in one launch of es_box3d_iou_filter behind es_topk_sorted.  It is not the head's NMS
+(bbox_head.predict: per class, BEV IoU, hundreds to thousands of boxes per prefix) and changes nothing there: everything here is opt-in.
+The IoU of a candidate row i with a kept row j is the [i][j] element of es_box3d_iou -- the candidate is the first argument -- and is
+compared in f32, like the score, against the f32 value of the threshold; a NaN IoU (zero-volume pair) does not suppress."""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import hip
+from .structures import EulerDepthInstance3DBoxes, InstanceData
+
+MAX_ROWS, MAX_CLASSES = 16384, 4096          # limits of es_topk_sorted / es_box3d_iou_filter
+
+
+def filter_instances(instances, iou_thr=0.15, score_thr=0.075, topk_per_class=10, n_classes=None):
+    """what bbox_head.predict / DetWalk.observe return -> InstanceData(bboxes_3d, scores_3d, labels_3d, keep) of the demo's object
+    list, in selection order (score descending, ties to the lower row); `keep` = int64 rows of the input.  n_classes None: max(label)
+    + 1, which costs one read-back (detectors pass bbox_head.num_classes); a row with a label outside [0, n_classes) is never kept.
+    The only host synchronisation otherwise is the read of the kept count.  ValueError before any launch: inputs on different
+    devices, more than 16384 rows, n_classes outside 1 .. 4096, topk_per_class < 1."""
+    boxes = getattr(instances.bboxes_3d, 'tensor', instances.bboxes_3d)
+    scores, labels = instances.scores_3d, instances.labels_3d
+    if not (boxes.device == scores.device == labels.device):
+        raise ValueError(f'filter_instances: boxes on {boxes.device}, scores on {scores.device}, labels on {labels.device}')
+    n = int(boxes.shape[0])
+    if boxes.dim() != 2 or boxes.shape[1] != 9 or scores.shape != (n,) or labels.shape != (n,):
+        raise ValueError(f'filter_instances: boxes (n, 9), scores (n), labels (n); got {tuple(boxes.shape)}, {tuple(scores.shape)}, '
+                         f'{tuple(labels.shape)}')
+    if n > MAX_ROWS:
+        raise ValueError(f'filter_instances: {n} rows, the sorted order covers {MAX_ROWS} (raise the head\'s score_thr or lower nms_pre)')
+    if topk_per_class < 1:
+        raise ValueError(f'filter_instances: topk_per_class = {topk_per_class}')
+    if n_classes is None:
+        n_classes = max(int(labels.max()) + 1, 1) if n else 1
+    if not 1 <= n_classes <= MAX_CLASSES:
+        raise ValueError(f'filter_instances: n_classes = {n_classes}, the class counters cover 1 .. {MAX_CLASSES}')
+    dev, P, st = boxes.device, hip.P, hip.stream()
+    b, s, l = boxes.float().contiguous(), scores.float().contiguous(), labels.to(torch.int32).contiguous()
+    order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    keep_idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    keep_cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    if n:
+        hip.call('es_topk_sorted', P(s), 1, n, 0, n, P(order), st)
+    hip.call('es_box3d_iou_filter', P(b), P(s), P(l), P(order), n, int(n_classes), float(iou_thr), float(score_thr), int(topk_per_class),
+             P(keep_idx), P(keep_cnt), st)
+    keep = keep_idx[:int(keep_cnt.item())].long()
+    return InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(boxes[keep]), scores_3d=scores[keep], labels_3d=labels[keep], keep=keep)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the folder
+CAM_AXES = np.array([[0., 0., 1.], [-1., 0., 0.], [0., -1., 0.]])       # demo.py:180: the recorder's camera axes -> the model's
+
+
+def quat_to_matrix(q):
+    """(x, y, z, w), scalar last, any non-zero norm -> 3 x 3 rotation (f64), as scipy's Rotation.from_quat(q).as_matrix()"""
+    q = np.asarray(q, np.float64)
+    nrm = float(np.sqrt((q * q).sum()))
+    if q.shape != (4,) or not nrm > 0:
+        raise ValueError(f'a quaternion has four components and a non-zero norm, got {q.tolist()}')
+    x, y, z, w = q / nrm
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def _matrix44(path):
+    m = np.loadtxt(path)
+    if m.shape != (4, 4):
+        raise ValueError(f'{path}: a 4 x 4 matrix, got shape {m.shape}')
+    return m
+
+
+def scene_info(scene_dir, origin=(0, 0, .5), depth_shift=1000., skip_first=True):
+    """The folder of the reference's demo (demo.py:143-197) -> the `info` dict ScanPipeline.__call__ consumes (numpy f64 throughout,
+    no scipy).  poses.txt: `timestamp x y z qx qy qz qw` per line; cam2global = [R(q) CAM_AXES | t]; extrinsic_i = inv(axis_align @
+    cam2global_i) as f32; frames rgb/<timestamp>.jpg and depth/<timestamp>.png; depth_cam2img = cam2img = intrinsic; empty ground
+    truth; scan_id = sample_idx = demo/<scene>.
+
+    skip_first: the reference's loop starts at line 1 of poses.txt and never uses line 0 -- kept as the default so that the same
+    folder gives the same frames; skip_first=False uses every line.
+    ValueError: intrinsic.txt / axis_align_matrix.txt not 4 x 4, a malformed pose line.  FileNotFoundError naming the first missing
+    frame file, before anything is decoded."""
+    scene_dir = os.path.abspath(scene_dir)
+    scene = os.path.basename(scene_dir.rstrip(os.sep))
+    axis_align = _matrix44(os.path.join(scene_dir, 'axis_align_matrix.txt'))
+    intrinsic = _matrix44(os.path.join(scene_dir, 'intrinsic.txt')).astype(np.float32)
+    with open(os.path.join(scene_dir, 'poses.txt')) as f:
+        lines = [ln for ln in f.read().splitlines() if ln.strip()]
+    images, img_path, depth_path, extrinsic = [], [], [], []
+    for k, ln in enumerate(lines[1 if skip_first else 0:], 1 if skip_first else 0):
+        tok = ln.split()
+        if len(tok) != 8:
+            raise ValueError(f'{scene_dir}/poses.txt line {k}: `timestamp x y z qx qy qz qw`, got {len(tok)} fields')
+        stamp, vals = tok[0], [float(v) for v in tok[1:]]
+        c2g = np.identity(4)
+        c2g[:3, :3] = quat_to_matrix(vals[3:]) @ CAM_AXES
+        c2g[:3, 3] = vals[:3]                                            # camera -> the recording's (not yet aligned) global frame
+        images.append(dict(img_path=os.path.join('demo', scene, 'rgb', stamp + '.jpg'),
+                           depth_path=os.path.join('demo', scene, 'depth', stamp + '.png'), cam2global=c2g, cam2img=intrinsic))
+        img_path.append(os.path.join(scene_dir, 'rgb', stamp + '.jpg'))
+        depth_path.append(os.path.join(scene_dir, 'depth', stamp + '.png'))
+        extrinsic.append(np.linalg.inv(axis_align @ c2g).astype(np.float32))
+    for p in (q for pair in zip(img_path, depth_path) for q in pair):
+        if not os.path.isfile(p):
+            raise FileNotFoundError(p)
+    V = len(images)
+    return dict(scan_id=f'demo/{scene}', sample_idx=f'demo/{scene}', axis_align_matrix=axis_align, images=images, img_path=img_path,
+                depth_img_path=depth_path,
+                depth2img=dict(extrinsic=extrinsic, intrinsic=intrinsic, origin=np.asarray(origin, np.float32)),
+                depth_cam2img=intrinsic, depth_shift=float(depth_shift), cam2img=intrinsic, box_type_3d='euler-depth',
+                ann_info=dict(gt_bboxes_3d=np.zeros((0, 9), np.float32), gt_labels_3d=np.zeros((0,), np.int64),
+                              visible_instance_masks=[[] for _ in range(V)], gt_occupancy=np.zeros((0, 4), np.int64),
+                              visible_occupancy_masks=[[] for _ in range(V)]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the model
+def init_model(config, checkpoint=None, device='cuda:0'):
+    """config: a path or a loaded config dict -> (detector in eval mode on `device`, cfg); checkpoint None: the seeded initialisation"""
+    from .checkpoint import load_checkpoint
+    from .config import build_detector, load_config
+    cfg = load_config(config) if isinstance(config, (str, os.PathLike)) else config
+    det = build_detector(cfg, device=device).to(device)
+    if checkpoint is not None:
+        load_checkpoint(det, checkpoint)
+    det.train(False)
+    return det, cfg
+
+
+def pipeline_of(cfg):
+    """cfg.test_dataloader.dataset.pipeline; a config that carries no test dataloader: its val dataloader's, else its `test_pipeline`"""
+    for key in ('test_dataloader', 'val_dataloader'):
+        if cfg.get(key) is not None:
+            return cfg[key]['dataset']['pipeline']
+    return cfg['test_pipeline']
+
+
+def _kind(detector):
+    from .models.detectors.dense_fusion_occ import DenseFusionOccPredictor
+    from .models.detectors.embodied_det3d import Embodied3DDetector
+    from .models.detectors.embodied_occ import EmbodiedOccPredictor
+    if isinstance(detector, EmbodiedOccPredictor):
+        return 'cont-occ'
+    if isinstance(detector, Embodied3DDetector):
+        return 'cont-det3d'
+    if isinstance(detector, DenseFusionOccPredictor):
+        return 'occ'
+    if hasattr(getattr(detector, 'bbox_head', None), 'num_classes') and not hasattr(detector, 'text_encoder'):
+        return 'det3d'
+    raise ValueError(f'{type(detector).__name__}: run_scene / walk_scene serve the detection and occupancy models (a grounder needs a prompt)')
+
+
+def load_scene(detector, scene_dir, pipeline, seed=0):
+    """scene_info -> ScanPipeline.from_cfg(pipeline) with numpy RandomState(seed) -> the scan on the detector's device"""
+    from . import pipeline as PL
+    from .datasets.loading import ScanPipeline
+    scan = ScanPipeline.from_cfg(pipeline)(scene_info(scene_dir), np.random.RandomState(seed))
+    return PL.upload_scan(scan, detector.device)
+
+
+def make_scene_batch(detector, dscan):
+    """the batch builder of the detector's kind on a scan without ground truth (the continuous kinds: one cloud per prefix)"""
+    from . import pipeline as PL
+    kind = _kind(detector)
+    if kind == 'cont-det3d':
+        return PL.make_cont_det_batch(dscan)
+    if kind == 'cont-occ':
+        data = PL.make_batch([dscan])
+        pts = data['inputs']['points'][0]
+        data['inputs']['points'] = [pts[:e] for e in PL.prefix_lengths(dscan['points_slice_indices'], pts.shape[0])]
+        ds = data['data_samples'][0]
+        ds.gt_occupancy = torch.zeros((0, 4), dtype=torch.int64)
+        ds.gt_occupancy_masks = [None] * len(data['inputs']['points'])      # (per prefix: what makes the preprocessor split the sample)
+        return data
+    return PL.make_batch([dscan])
+
+
+def _filtered(detector, inst, filter):
+    if filter is None:
+        return inst
+    return filter_instances(inst, **dict(dict(n_classes=detector.bbox_head.num_classes), **filter))
+
+
+def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict()):
+    """one `predict` over the folder.  Detectors: the filtered InstanceData per sample (the cont-det3d detector: one per prefix);
+    occupancy models: pred_occupancy per sample / prefix.  filter: keyword arguments of filter_instances; None: the raw prediction"""
+    kind = _kind(detector)
+    data = detector.data_preprocessor(make_scene_batch(detector, load_scene(detector, scene_dir, pipeline, seed)), False)
+    out = detector.forward(data['inputs'], data['data_samples'], mode='predict')
+    if kind in ('occ', 'cont-occ'):
+        return [ds.pred_occupancy for ds in out]
+    return [_filtered(detector, ds.pred_instances_3d, filter) for ds in out]
+
+
+def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None):
+    """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene without the
+    rendering): opens a walk session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy)"""
+    from . import pipeline as PL
+    kind = _kind(detector)
+    if kind not in ('cont-det3d', 'cont-occ'):
+        raise ValueError(f'{type(detector).__name__} has no walk session: use run_scene')
+    dscan = load_scene(detector, scene_dir, pipeline, seed)
+    batch = make_scene_batch(detector, dscan)
+    cloud = batch['inputs']['points'][-1]
+    data = detector.data_preprocessor(batch, False)
+    imgs = data['inputs']['imgs'].clone()                                # (the preprocessor's buffers are a ring)
+    meta = dict(data['data_samples'][0].metainfo)
+    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
+    meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
+    n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
+    walk = detector.open_walk(meta, max_frames=max(n_frames, 1)) if kind == 'cont-det3d' else detector.open_walk(meta)
+    for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
+        if t >= n_frames:
+            break
+        res = walk.observe(imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
+        yield t, (res if kind == 'cont-occ' else _filtered(detector, res, filter))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the command line
+def _class_names(cfg, n):
+    mi = cfg.get('metainfo') or {}
+    names = list(mi.get('classes', ())) if isinstance(mi, dict) else []
+    return names if len(names) >= n else names + [f'class_{i}' for i in range(len(names), n)]
+
+
+def _record(res, names, **extra):
+    if isinstance(res, InstanceData):
+        labels = res.labels_3d.cpu().tolist()
+        return dict(extra, boxes=res.bboxes_3d.tensor.cpu().tolist(), scores=res.scores_3d.cpu().tolist(), labels=labels,
+                    class_names=[names[l] for l in labels])
+    hist = torch.bincount(res.reshape(-1)).cpu().tolist()
+    return dict(extra, shape=list(res.shape), class_histogram=hist)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog='python -m embodiedscan_amd.inference', description=__doc__.split('\n\n')[0])
+    ap.add_argument('config')
+    ap.add_argument('checkpoint', nargs='?', default=None)
+    ap.add_argument('--root-dir', required=True, help='directory that holds the scene folders')
+    ap.add_argument('--scene', default='office')
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--walk', action='store_true', help='frame by frame through a walk session (continuous models)')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--iou-thr', type=float, default=0.15)
+    ap.add_argument('--score-thr', type=float, default=0.075)
+    ap.add_argument('--topk-per-class', type=int, default=10)
+    ap.add_argument('--out', default=None, help='JSON file (default: standard output)')
+    a = ap.parse_args(argv)
+    det, cfg = init_model(a.config, a.checkpoint, a.device)
+    scene_dir = os.path.join(a.root_dir, a.scene)
+    flt = dict(iou_thr=a.iou_thr, score_thr=a.score_thr, topk_per_class=a.topk_per_class)
+    pipe = pipeline_of(cfg)
+    kind = _kind(det)
+    nc = getattr(det.bbox_head, 'num_classes', 0)
+    names = _class_names(cfg, nc) if kind in ('det3d', 'cont-det3d') else ['empty'] + _class_names(cfg, max(nc - 1, 0))
+    if a.walk:
+        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt)]
+    else:
+        results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt))]
+    doc = json.dumps(dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt,
+                          results=results))
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(doc)
+    else:
+        print(doc)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

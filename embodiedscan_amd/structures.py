@@ -28,6 +28,18 @@ class EulerDepthInstance3DBoxes:
     def volume(self):
         return self.tensor[:, 3] * self.tensor[:, 4] * self.tensor[:, 5]
 
+    @classmethod
+    def overlaps(cls, boxes1, boxes2):
+        """(N, M) f32 IoU of two box sets on the device (euler_box3d.py:103-135 -> pytorch3d box3d_overlap; here es_box3d_iou:
+        f64 polyhedral clipping rounded to f32).  Boxes or (n, 9) tensors, both on the device the kernels run on."""
+        from . import hip
+        a, b = (getattr(x, 'tensor', x).float().contiguous() for x in (boxes1, boxes2))
+        if a.device != b.device:
+            raise ValueError(f'overlaps: both box sets on one device, got {a.device} and {b.device}')
+        out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+        hip.call('es_box3d_iou', hip.P(a), a.shape[0], hip.P(b), b.shape[0], hip.P(out), hip.stream())
+        return out
+
     def to(self, device):
         b = EulerDepthInstance3DBoxes(self.tensor.to(device))
         return b

@@ -285,3 +285,63 @@ def write_dataset(root, n_scans=2, n_frames=6, height=60, width=80, n_boxes=6, c
     with open(os.path.join(root, 'embodiedscan_train_vg.json'), 'w') as f:
         json.dump(vg, f)
     return scans, class_names
+
+
+def _matrix_to_quat(m):
+    """3 x 3 rotation -> (x, y, z, w), scalar last, w >= 0 (the branch of the largest diagonal term: no division by a small number)"""
+    t = [m[0, 0], m[1, 1], m[2, 2], m[0, 0] + m[1, 1] + m[2, 2]]
+    k = int(np.argmax(t))
+    if k == 3:
+        q = np.array([m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1], 1.0 + t[3]])
+    else:
+        i, j, l = k, (k + 1) % 3, (k + 2) % 3
+        q = np.zeros(4)
+        q[i] = 1.0 + m[i, i] - m[j, j] - m[l, l]
+        q[j] = m[j, i] + m[i, j]
+        q[l] = m[l, i] + m[i, l]
+        q[3] = m[l, j] - m[j, l]
+    q = q / np.linalg.norm(q)
+    return q if q[3] >= 0 else -q
+
+
+def write_demo_scene(root, scene, n_frames=4, height=60, width=80, seed=0, n_boxes=6, jpeg_quality=90):
+    """Write a make_scan scan (unaugmented) in the folder layout the reference's demo reads (demo/demo.py:143-197; read back by
+    inference.scene_info): root/scene/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}.
+    JPEG colour frames, 16-bit PNG depth in millimetres.  poses.txt holds `timestamp x y z qx qy qz qw` (scalar last) of
+    cam2global = inv(axis_align) @ inv(extrinsic), with the camera axes of the recorder: R(q) = cam2global[:3, :3] @ CAM_AXES^T --
+    the inverse of the convention scene_info applies.  The demo never uses line 0 of poses.txt, so the n_frames poses of the scan
+    are lines 1 .. n_frames behind one extra line (timestamp `00000`, the identity pose, copies of frame 1's files so that reading
+    every line works too).  Returns dict(scan, axis_align (4,4), cam2global [n_frames x (4,4)], timestamps, scene_dir)."""
+    import os
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    scan = make_scan(seed, n_views=n_frames, height=height, width=width, img_size=(height, width), n_boxes=n_boxes, n_points=2000,
+                     augment=False)
+    A = np.eye(4)
+    A[:3, :3] = _euler_zxy([rng.uniform(-math.pi, math.pi), 0, 0])
+    A[:3, 3] = rng.uniform(-1, 1, 3)
+    Ainv = np.linalg.inv(A)
+    cam_axes = np.array([[0., 0., 1.], [-1., 0., 0.], [0., -1., 0.]])
+    scene_dir = os.path.join(root, scene)
+    for sub in ('rgb', 'depth'):
+        os.makedirs(os.path.join(scene_dir, sub), exist_ok=True)
+    np.savetxt(os.path.join(scene_dir, 'axis_align_matrix.txt'), A, fmt='%.17g')
+    np.savetxt(os.path.join(scene_dir, 'intrinsic.txt'), scan['intrinsic'][0].astype(np.float64), fmt='%.17g')
+    yy, xx = np.meshgrid(np.arange(height), np.arange(width), indexing='ij')
+    stamps, c2gs, lines = [], [], ['00000 0 0 0 0 0 0 1']
+    for v in range(n_frames):
+        stamp = f'{v + 1:05d}'
+        base = np.stack([(xx * (3 + v) + seed * 17) % 256, (yy * (2 + v)) % 256, ((xx + yy) * 2 + 40 * v) % 256], -1)
+        img = np.clip(base + rng.integers(-12, 13, base.shape), 0, 255).astype(np.uint8)
+        mm = np.clip(np.rint(scan['depth'][v] * 1000.0), 0, 65535).astype(np.uint16)
+        for s in ([stamp, '00000'] if v == 0 else [stamp]):
+            Image.fromarray(img).save(os.path.join(scene_dir, 'rgb', s + '.jpg'), quality=jpeg_quality)
+            Image.fromarray(np.ascontiguousarray(mm)).save(os.path.join(scene_dir, 'depth', s + '.png'))
+        c2g = Ainv @ np.linalg.inv(scan['extrinsic'][v].astype(np.float64))
+        q = _matrix_to_quat(c2g[:3, :3] @ cam_axes.T)
+        lines.append(' '.join([stamp] + ['%.17g' % x for x in list(c2g[:3, 3]) + list(q)]))
+        stamps.append(stamp)
+        c2gs.append(c2g)
+    with open(os.path.join(scene_dir, 'poses.txt'), 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+    return dict(scan=scan, axis_align=A, cam2global=c2gs, timestamps=stamps, scene_dir=scene_dir)

@@ -589,6 +589,16 @@ int es_ground_decode_fcaf_bwd(const float* pred, int ldp, const float* dbox, int
                               void* stream);
 /* N2: exact IoU of 9-DoF Euler (ZXY) boxes, (N,M) -- EulerInstance3DBoxes.overlaps / pytorch3d box3d_overlap */
 int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int M, float* iou, void* stream);
+/* The demo's object list (demo/demo.py:84-130 nms_filter) in one launch: boxes (n,9), scores (n), labels (n) int32, order (n) =
+ * es_topk_sorted(scores, B = 1, L = n, k = n) (score descending, ties to the lower row).  Walking `order`, a row is skipped when its
+ * class already holds topk_per_class kept rows, when score < score_thr, or when iou(row, j) > iou_thr for ANY kept row j (class
+ * agnostic); otherwise it is kept.  iou(row, j) = the [row][j] element es_box3d_iou(boxes, n, boxes, n) stores (f64 polyhedral,
+ * the candidate as the first argument, rounded to f32); both comparisons are f32, so a NaN IoU (zero-volume pair) does not
+ * suppress.  A row whose label is outside [0, n_classes) is never kept.  keep_idx[0 .. keep_cnt) = the kept rows in selection
+ * order, nothing is written beyond; keep_cnt (1).  n = 0: keep_cnt = 0.  NaN scores are outside the contract.
+ * -4, nothing written: n > 16384 (es_topk_sorted's limit), n_classes outside 1 .. 4096, topk_per_class < 1; -5: n < 0. */
+int es_box3d_iou_filter(const float* boxes, const float* scores, const int* labels, const int* order, int n, int n_classes,
+                        float iou_thr, float score_thr, int topk_per_class, int* keep_idx, int* keep_cnt, void* stream);
 /* N5: IndoorDetMetric on the device (embodiedscan/eval/indoor_eval.py:8-182).  Ground-truth rows are ordered by (scene, class)
  * group, grp_off_dev (n_grp+1) delimits the groups, pred_grp (P) is a prediction's group or -1.
  * es_det_best_gt: predictions with a face below 2e-4 have their sizes clamped to 2e-2; iou_max (P) = the highest f64 polyhedral IoU
