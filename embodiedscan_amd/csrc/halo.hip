@@ -48,19 +48,11 @@ __device__ __attribute__((aligned(16))) unsigned short g_hl_zero[8];
 // loc[row][k] = position of nbr[row][k] in that list (0xFFFF: absent).  loc / hrows are padded to whole tiles by the caller.
 // The tile's 6 912 map entries are staged in LDS with coalesced 16-byte loads and the positions leave as coalesced words (the
 // first version read and wrote them per row, 108 / 54 bytes apart between neighbouring lanes: 131 us on 1 480 tiles).
-__global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, int n_out, int K,
-                                                   unsigned short* __restrict__ loc, int* __restrict__ hrows,
-                                                   int* __restrict__ hcnt) {
-  constexpr int NE = HL_BM * HL_K;                  // map entries of a tile
-  __shared__ __attribute__((aligned(16))) int nb[NE];     // the tile's entries; after the inserts: the list of distinct rows
-  __shared__ unsigned short slotOf[NE];             // hash slot of every entry (0xFFFF: absent neighbour)
-  __shared__ int hk[HL_HT];
-  __shared__ unsigned short hv[HL_HT];
-  __shared__ int cnt;
-  const int t = threadIdx.x, tile = blockIdx.x;
+// the tile's map entries -> nb (LDS), absent past the map's end
+__device__ __forceinline__ void halo_plan_stage(const int* __restrict__ nbr, int n_out, int K, int tile, int* nb) {
+  constexpr int NE = HL_BM * HL_K;
+  const int t = threadIdx.x;
   const long long e0 = (long long)tile * NE, eN = (long long)n_out * K;
-  for (int i = t; i < HL_HT; i += 512) hk[i] = -1;
-  if (t == 0) cnt = 0;
   for (int i = t; i < NE / 4; i += 512) {           // (e0 is a multiple of 4: 16-byte aligned)
     int4 v = make_int4(-1, -1, -1, -1);
     const long long e = e0 + (long long)i * 4;
@@ -72,7 +64,13 @@ __global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, 
     }
     ((int4*)nb)[i] = v;
   }
-  __syncthreads();
+}
+// hash-and-rank plan of the staged tile (the caller has set hk[] = -1 and *cntp = 0 and passed a barrier): an 8 192-slot LDS hash with one
+// CAS per entry, the occupied slots compacted to a list, the list ranked by counting
+__device__ __forceinline__ void halo_plan_hash(int tile, int* nb, unsigned short* slotOf, int* hk, unsigned short* hv, int* cntp,
+                                               unsigned short* __restrict__ loc, int* __restrict__ hrows, int* __restrict__ hcnt) {
+  constexpr int NE = HL_BM * HL_K;
+  const int t = threadIdx.x;
   for (int e = t; e < NE; e += 512) {
     const int v = nb[e];
     unsigned short so = 0xFFFFu;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, 
     const int v = hk[sl];                           // one counter atomic per wave and round, not one per distinct row
     const unsigned long long m = __ballot(v >= 0);
     int base = 0;
-    if ((t & 63) == 0 && m) base = atomicAdd(&cnt, __popcll(m));
+    if ((t & 63) == 0 && m) base = atomicAdd(cntp, __popcll(m));
     base = __shfl(base, 0, 64);
     if (v >= 0) {
       const int pos = base + __popcll(m & ((1ull << (t & 63)) - 1ull));
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, 
     }
   }
   __syncthreads();
-  const int nU = cnt;
+  const int nU = *cntp;
   unsigned short* const rk = (unsigned short*)hk;   // list index -> rank (the keys are dead: every slot knows its list index)
   int* const hr = hrows + (size_t)tile * NE;
   for (int i = t; i < nU; i += 512) {               // rank by counting (nU ~ 300 .. 700: broadcast reads)
@@ -121,14 +119,142 @@ __global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, 
     dst[i] = p0 | (p1 << 16);
   }
 }
+__global__ __launch_bounds__(512) void k_halo_plan(const int* __restrict__ nbr, int n_out, int K,
+                                                   unsigned short* __restrict__ loc, int* __restrict__ hrows,
+                                                   int* __restrict__ hcnt) {
+  constexpr int NE = HL_BM * HL_K;                  // map entries of a tile
+  __shared__ __attribute__((aligned(16))) int nb[NE];     // the tile's entries; after the inserts: the list of distinct rows
+  __shared__ unsigned short slotOf[NE];             // hash slot of every entry (0xFFFF: absent neighbour)
+  __shared__ int hk[HL_HT];
+  __shared__ unsigned short hv[HL_HT];
+  __shared__ int cnt;
+  const int t = threadIdx.x, tile = blockIdx.x;
+  for (int i = t; i < HL_HT; i += 512) hk[i] = -1;
+  if (t == 0) cnt = 0;
+  halo_plan_stage(nbr, n_out, K, tile, nb);
+  __syncthreads();
+  halo_plan_hash(tile, nb, slotOf, hk, hv, &cnt, loc, hrows, hcnt);
+}
+
+// The same plan by BITMAP (es_halo_set_option 32, default on).  The distinct source rows of a tile lie in a narrow index range (a
+// Z-ordered set: the 27-neighbourhoods of 256 consecutive rows), so sorting them is marking them: one bit per index of the span
+// [min, max] of the tile's present entries, one atomicOr per entry, a popcount per word, an exclusive scan over the words -- the
+// position of a row in the sorted list is the prefix of its word plus the set bits below its own.  No hash, no CAS chains, no ranking
+// loop.  Taken per tile, block-uniformly, while the span is at most 2^19 indices (64 KB of bitmap + 32 KB of 16-bit prefixes -- counts
+// are <= 6 912 -- + the 27.6 KB entry tile: 124 KB, one workgroup per CU as before); a tile with a wider span runs the hash-and-rank
+// code above in the same LDS.  Same hrows[0 .. hcnt) / loc / hcnt, bit for bit (tests/test_gpu_halo_plan_bitmap.py).
+#define HL_SPAN (1 << 19)
+#define HL_WORDS (HL_SPAN / 32)
+__global__ __launch_bounds__(512) void k_halo_plan_bitmap(const int* __restrict__ nbr, int n_out, int K,
+                                                          unsigned short* __restrict__ loc, int* __restrict__ hrows,
+                                                          int* __restrict__ hcnt) {
+  constexpr int NE = HL_BM * HL_K;
+  constexpr int OFF_BM = NE * 4, OFF_PRE = OFF_BM + HL_WORDS * 4, OFF_END = OFF_PRE + HL_WORDS * 2;
+  static_assert(OFF_BM + NE * 2 + HL_HT * 4 + HL_HT * 2 <= OFF_END, "the hash path's tables live in the bitmap's LDS");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[OFF_END];
+  __shared__ int redMin[8], redMax[8], wtot[8];
+  __shared__ int cnt;
+  int* const nb = (int*)smem;
+  unsigned int* const bm = (unsigned int*)(smem + OFF_BM);
+  unsigned short* const pre = (unsigned short*)(smem + OFF_PRE);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, tile = blockIdx.x;
+  halo_plan_stage(nbr, n_out, K, tile, nb);
+  __syncthreads();
+  int mn = 0x7FFFFFFF, mx = -1;                     // span of the present entries
+  for (int e = t; e < NE; e += 512) {
+    const int v = nb[e];
+    if (v >= 0) { mn = min(mn, v); mx = max(mx, v); }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    mn = min(mn, __shfl_xor(mn, d, 64));
+    mx = max(mx, __shfl_xor(mx, d, 64));
+  }
+  if (lane == 0) { redMin[wv] = mn; redMax[wv] = mx; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 8; ++w) { mn = min(mn, redMin[w]); mx = max(mx, redMax[w]); }
+  const long long span = mx >= 0 ? (long long)mx - mn + 1 : 0;     // (0: every entry absent)
+  if (span > HL_SPAN) {                             // block-uniform: the hash-and-rank plan in the same LDS
+    unsigned short* const slotOf = (unsigned short*)(smem + OFF_BM);
+    int* const hk = (int*)(smem + OFF_BM + NE * 2);
+    unsigned short* const hv = (unsigned short*)(smem + OFF_BM + NE * 2 + HL_HT * 4);
+    for (int i = t; i < HL_HT; i += 512) hk[i] = -1;
+    if (t == 0) cnt = 0;
+    __syncthreads();
+    halo_plan_hash(tile, nb, slotOf, hk, hv, &cnt, loc, hrows, hcnt);
+    return;
+  }
+  const int nW = (int)((span + 31) >> 5);           // <= HL_WORDS
+  for (int w = t; w < nW; w += 512) bm[w] = 0u;
+  __syncthreads();
+  for (int e = t; e < NE; e += 512) {
+    const int v = nb[e];
+    if (v >= 0) atomicOr(&bm[(unsigned)(v - mn) >> 5], 1u << ((v - mn) & 31));
+  }
+  __syncthreads();
+  // thread t owns the words [t * per, t * per + per): their set bits, an exclusive scan over the threads, then the words' prefixes
+  // and the rows themselves in ascending order
+  const int per = (nW + 511) >> 9;                  // <= 32
+  const int w0 = t * per, w1 = min(nW, w0 + per);
+  int mine = 0;
+  for (int w = w0; w < w1; ++w) mine += __popc(bm[w]);
+  int inc = mine;                                   // inclusive scan over the wave ...
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) wtot[wv] = inc;
+  __syncthreads();
+  int run = inc - mine;                             // ... + the waves before this one
+  int nU = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    if (w < wv) run += wtot[w];
+    nU += wtot[w];
+  }
+  int* const hr = hrows + (size_t)tile * NE;
+  for (int w = w0; w < w1; ++w) {
+    unsigned int bits = bm[w];
+    pre[w] = (unsigned short)run;
+    while (bits) {
+      const int b = __ffsll((unsigned long long)bits) - 1;
+      bits &= bits - 1u;
+      hr[run++] = mn + w * 32 + b;
+    }
+  }
+  if (t == 0) hcnt[tile] = nU;
+  __syncthreads();
+  unsigned int* const dst = (unsigned int*)(loc + (size_t)tile * NE);
+  for (int i = t; i < NE / 2; i += 512) {
+    unsigned int p[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int v = nb[2 * i + h];
+      p[h] = 0xFFFFu;
+      if (v >= 0) {
+        const unsigned int o = (unsigned int)(v - mn);
+        p[h] = (unsigned int)pre[o >> 5] + (unsigned int)__popc(bm[o >> 5] & ((1u << (o & 31)) - 1u));
+      }
+    }
+    dst[i] = p[0] | (p[1] << 16);
+  }
+}
+
+static int ES_OPT_HALO_PLAN_BITMAP = 1;   // es_halo_set_option 32: es_halo_plan on k_halo_plan_bitmap (0: k_halo_plan, the hash-and-rank plan for every tile)
 
 extern "C" size_t es_halo_plan_rows(int n_out) { return (size_t)es_cdiv(n_out, HL_BM) * HL_BM; }
 
 extern "C" int es_halo_plan(const int* nbr, int n_out, int K, void* loc, int* hrows, int* hcnt, void* stream) {
   if (n_out <= 0) return 0;
   if (K != HL_K || nbr == nullptr) return -4;
-  hipLaunchKernelGGL(k_halo_plan, dim3(es_cdiv(n_out, HL_BM)), dim3(512), 0, (hipStream_t)stream, nbr, n_out, K,
-                     (unsigned short*)loc, hrows, hcnt);
+  if (ES_OPT_HALO_PLAN_BITMAP)
+    hipLaunchKernelGGL(k_halo_plan_bitmap, dim3(es_cdiv(n_out, HL_BM)), dim3(512), 0, (hipStream_t)stream, nbr, n_out, K,
+                       (unsigned short*)loc, hrows, hcnt);
+  else
+    hipLaunchKernelGGL(k_halo_plan, dim3(es_cdiv(n_out, HL_BM)), dim3(512), 0, (hipStream_t)stream, nbr, n_out, K,
+                       (unsigned short*)loc, hrows, hcnt);
   ES_CHECK_LAUNCH();
   return 0;
 }
@@ -373,6 +499,7 @@ static int ES_OPT_HALO_MIN_WGS = 192;     // the halo kernel takes launches with
 extern "C" int es_halo_set_option(int key, int value) {
   if (key == 30) { ES_OPT_HALO_MIN_WGS = value; return 0; }
   if (key == 31) { ES_OPT_HALO_WGS = value; return 0; }
+  if (key == 32) { ES_OPT_HALO_PLAN_BITMAP = value; return 0; }
   return -1;
 }
 

@@ -13,6 +13,22 @@
 #include "../../include/es_hip.h"
 
 // ------------------------------------------------------------------ focal
+// loss l and dloss/dlogit g of one (row, class) element; pos: the class is the row's label
+__device__ __forceinline__ void focal_elem(float x, bool pos, bool g2, float gamma, float alpha, float& l, float& g) {
+  float p = 1.f / (1.f + expf(-x));
+  if (pos) {
+    float q = 1.f - p;
+    float lp = logf(fmaxf(p, 1.17549435e-38f));
+    float w = g2 ? q * q : powf(q, gamma);
+    l = -alpha * w * lp;
+    g = -alpha * w * (1.f - p - gamma * p * lp);
+  } else {
+    float ln = logf(fmaxf(1.f - p, 1.17549435e-38f));
+    float w = g2 ? p * p : powf(p, gamma);
+    l = -(1.f - alpha) * w * ln;
+    g = -(1.f - alpha) * w * (gamma * (1.f - p) * ln - p);
+  }
+}
 // one wave per row, lanes stride over the classes: coalesced, no 64-bit index division; gamma == 2 (the shipped value)
 // squares instead of calling powf
 __global__ __launch_bounds__(256) void k_focal(const float* __restrict__ logits, int ldl,
@@ -32,23 +48,76 @@ __global__ __launch_bounds__(256) void k_focal(const float* __restrict__ logits,
     float* grow = grad ? grad + (size_t)i * ldg : nullptr;
     float acc = 0.f;
     for (int c = lane; c < C; c += 64) {
-      float x = row[c];
-      float p = 1.f / (1.f + expf(-x));
       float l, g;
-      if (lab == c) {
-        float q = 1.f - p;
-        float lp = logf(fmaxf(p, 1.17549435e-38f));
-        float w = g2 ? q * q : powf(q, gamma);
-        l = -alpha * w * lp;
-        g = -alpha * w * (1.f - p - gamma * p * lp);
-      } else {
-        float ln = logf(fmaxf(1.f - p, 1.17549435e-38f));
-        float w = g2 ? p * p : powf(p, gamma);
-        l = -(1.f - alpha) * w * ln;
-        g = -(1.f - alpha) * w * (gamma * (1.f - p) * ln - p);
-      }
+      focal_elem(row[c], lab == c, g2, gamma, alpha, l, g);
       acc += l;
       if (grow) grow[c] = g * inv;
+    }
+    if (grow) {
+      for (int c = lane; c < lead; c += 64) grow[c - lead] = 0.f;
+      for (int c = lane; c < tail; c += 64) grow[C + c] = 0.f;
+    }
+    s += (double)acc;
+  }
+  s = es_wave_sum_d(s);
+  if (lane == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+// k_focal for C <= 320 with its loads in flight: the same rows on the same waves, the same per-lane sum over c and per-wave sum over
+// rows -- only the issue order differs.  A lane loads its (up to five) logits of a row before the first expf, and the next row's logits
+// and label before the current row's arithmetic, so a wave keeps two rows (2 x 5 loads) in flight instead of one load.
+#define FOCAL_SLOTS 5
+__global__ __launch_bounds__(256) void k_focal_inflight(const float* __restrict__ logits, int ldl,
+                                                        const int* __restrict__ labels, int N, int C, float gamma,
+                                                        float alpha, const float* __restrict__ avg_factor, float grad_scale,
+                                                        float* __restrict__ grad, int ldg, double* __restrict__ partial, int lead,
+                                                        int tail) {
+  __shared__ double red[4];
+  const float inv = grad_scale / (avg_factor[0] + 1.1920929e-07f);
+  const bool g2 = gamma == 2.f;
+  const int lane = threadIdx.x & 63;
+  const int step = gridDim.x * 4;
+  double s = 0.0;
+  int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  float xn[FOCAL_SLOTS];
+  int labn = 0;
+#pragma unroll
+  for (int j = 0; j < FOCAL_SLOTS; ++j) xn[j] = 0.f;
+  if (i < N) {
+    const float* row = logits + (size_t)i * ldl;
+    labn = labels[i];
+#pragma unroll
+    for (int j = 0; j < FOCAL_SLOTS; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) xn[j] = row[c];
+    }
+  }
+  for (; i < N; i += step) {
+    float x[FOCAL_SLOTS];
+    const int lab = labn;
+#pragma unroll
+    for (int j = 0; j < FOCAL_SLOTS; ++j) x[j] = xn[j];
+    if (i + step < N) {                       // the next row of this wave: issued before the arithmetic below
+      const float* row = logits + (size_t)(i + step) * ldl;
+      labn = labels[i + step];
+#pragma unroll
+      for (int j = 0; j < FOCAL_SLOTS; ++j) {
+        const int c = lane + 64 * j;
+        if (c < C) xn[j] = row[c];
+      }
+    }
+    float* grow = grad ? grad + (size_t)i * ldg : nullptr;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < FOCAL_SLOTS; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) {
+        float l, g;
+        focal_elem(x[j], lab == c, g2, gamma, alpha, l, g);
+        acc += l;
+        if (grow) grow[c] = g * inv;
+      }
     }
     if (grow) {
       for (int c = lane; c < lead; c += 64) grow[c - lead] = 0.f;
@@ -75,6 +144,11 @@ __global__ void k_sum_partials(const double* __restrict__ partial, int n, const 
   }
 }
 #define FOCAL_BLOCKS 2048
+static int ES_OPT_FOCAL_INFLIGHT = 1;   // es_losses_set_option key 40: rows of at most 320 classes on k_focal_inflight (0: k_focal for every C)
+extern "C" int es_losses_set_option(int key, int value) {
+  if (key == 40) { ES_OPT_FOCAL_INFLIGHT = value; return 0; }
+  return -2;
+}
 // loss_out[0] += sum / (avg_factor + eps);  grad = dloss/dlogit * grad_scale.  partial: FOCAL_BLOCKS doubles.
 extern "C" int es_focal_loss(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
                              const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial,
@@ -93,8 +167,12 @@ extern "C" int es_focal_loss_clear(const float* logits, int ldl, const int* labe
   int g = es_cdiv(N, 4);
   if (g > FOCAL_BLOCKS) g = FOCAL_BLOCKS;
   if (g < 1) g = 1;
-  hipLaunchKernelGGL(k_focal, dim3(g), dim3(256), 0, st, logits, ldl, labels, N, C, gamma, alpha, avg_factor_dev,
-                     grad_scale, grad, ldg, partial, lead, tail);
+  if (ES_OPT_FOCAL_INFLIGHT && C <= 64 * FOCAL_SLOTS)
+    hipLaunchKernelGGL(k_focal_inflight, dim3(g), dim3(256), 0, st, logits, ldl, labels, N, C, gamma, alpha, avg_factor_dev,
+                       grad_scale, grad, ldg, partial, lead, tail);
+  else
+    hipLaunchKernelGGL(k_focal, dim3(g), dim3(256), 0, st, logits, ldl, labels, N, C, gamma, alpha, avg_factor_dev,
+                       grad_scale, grad, ldg, partial, lead, tail);
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, partial, g, avg_factor_dev, loss_out);
   ES_CHECK_LAUNCH();
   return 0;

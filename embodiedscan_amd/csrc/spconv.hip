@@ -108,6 +108,8 @@ __global__ __launch_bounds__(256) void k_spconv(const float* __restrict__ X, int
 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int row0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  const int mirror = accumulate & 2;                         // (bit 1 of the entry point's `accumulate`: mirrored tap walk)
+  accumulate &= 1;
   const bool vecA = ((ldx & 3) == 0) && ((((uintptr_t)X) & 15) == 0);
   const bool vecB = TRANS_W ? (((Cin & 3) == 0) && ((((uintptr_t)W) & 15) == 0))
                             : (((Cout & 3) == 0) && ((((uintptr_t)W) & 15) == 0));
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void k_spconv(const float* __restrict__ X, int
   for (int e = t; e < BM * K; e += 256) {
     int r = e / K, k = e - r * K;
     int j = row0 + r, v = -1;
-    if (j < n_out) v = nbr ? nbr[(size_t)j * K + k] : (j < n_in ? j : -1);
+    if (j < n_out) v = nbr ? nbr[(size_t)j * K + (mirror ? K - 1 - k : k)] : (j < n_in ? j : -1);
     nbrS[e] = v;
     if (v >= 0) tapAny[k] = 1;
   }
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(256) void k_spconv(const float* __restrict__ X, int
 #endif
 template <int CIN>
 __device__ __forceinline__ void narrow_stage(const float* __restrict__ X, int ldx, const int* __restrict__ nbr, int row0,
-                                             int n_out, int n_in, float* xg, int* idxS, int* maskS) {
+                                             int n_out, int n_in, float* xg, int* idxS, int* maskS, int mirror = 0) {
   const int t = threadIdx.x;
   // two rounds of INDEPENDENT loads (all map entries of this thread, then all input rows): two memory latencies per tile, not 2 x 7
   constexpr int NI = (NW_ROWS * 27 + 255) / 256;
@@ -281,7 +283,7 @@ __device__ __forceinline__ void narrow_stage(const float* __restrict__ X, int ld
   for (int i = 0; i < NI; ++i) {
     const int e = t + i * 256;
     v[i] = -1;
-    if (e < NW_ROWS * 27 && row0 + e / 27 < n_out) v[i] = nbr[(size_t)row0 * 27 + e];
+    if (e < NW_ROWS * 27 && row0 + e / 27 < n_out) v[i] = nbr[(size_t)row0 * 27 + (mirror ? e + 26 - 2 * (e % 27) : e)];
     if (v[i] >= n_in) v[i] = -1;
   }
   float xv[NI][CIN];
@@ -323,6 +325,8 @@ __global__ __launch_bounds__(256) void k_spconv_narrow_fwd(const float* __restri
   __shared__ int idxS[NW_ROWS * 27];
   __shared__ int maskS[NW_ROWS];
   const int t = threadIdx.x, co = t & 63, wv = t >> 6;
+  const int mirror = accumulate & 2;                         // (bit 1 of the entry point's `accumulate`)
+  accumulate &= 1;
   float w[27][CIN];
 #pragma unroll
   for (int k = 0; k < 27; ++k)
@@ -332,7 +336,7 @@ __global__ __launch_bounds__(256) void k_spconv_narrow_fwd(const float* __restri
   const int tiles = (n_out + NW_ROWS - 1) / NW_ROWS;
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int row0 = tile * NW_ROWS;
-    narrow_stage<CIN>(X, ldx, nbr, row0, n_out, n_in, xg, idxS, maskS);
+    narrow_stage<CIN>(X, ldx, nbr, row0, n_out, n_in, xg, idxS, maskS, mirror);
     for (int rr = 0; rr < NW_ROWS / 4; ++rr) {
       const int r = wv * (NW_ROWS / 4) + rr;
       if (row0 + r >= n_out) break;
@@ -360,6 +364,7 @@ extern "C" int es_spconv_fwd(const float* X, int ldx, const float* W, const int*
                              void* stream) {
   if (n_out <= 0 || Cout <= 0) return 0;
   if (K > MAXK) return -2;
+  if ((accumulate & 2) && (!(K & 1) || nbr == nullptr)) return -3;     // mirrored tap walk: an odd kernel on a real map
   if (!trans_w && narrow_ok(nbr, K, Cin, Cout)) {
     const int tiles = es_cdiv(n_out, NW_ROWS);
     hipLaunchKernelGGL(k_spconv_narrow_fwd<3>, dim3(tiles > 2048 ? 2048 : tiles), dim3(256), 0, (hipStream_t)stream, X, ldx, W, nbr,
@@ -665,6 +670,8 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // activation-storage flags of the image backbone (round 3): bit 0: the Y rows are bf16, bit 1: the ep_res rows are bf16
 #define ES_IO_Y16 1
 #define ES_IO_R16 2
+#define ES_IO_MIRROR 0x20000    // the map tile is staged with its taps mirrored: tap k of row j reads nbr[j * K + (K - 1 - k)] (a set's own odd-kernel
+                                // map read as its inverse map; entry points: bit 1 of `accumulate`)
 #define ES_IO_WSHARE 0x10000    // tap-split launches: workgroup order in which the row tiles of one (column tile, tap slice) share an XCD
 __device__ __forceinline__ float4 bf16x4_to_f32(uint2 v) {
   return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
@@ -702,6 +709,7 @@ __global__ __launch_bounds__(256) void k_spconv_bf16(const float* __restrict__ X
   __shared__ int tapAny[32];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int row0 = blockIdx.x * BM, n0 = blockIdx.y * BNT;
+  const int mirror = io & ES_IO_MIRROR;
   const bool vecA = ((ldx & 3) == 0) && ((((uintptr_t)X) & 15) == 0);
   const bool vecB = ((Cin & 7) == 0) && ((((uintptr_t)W) & 15) == 0);
 
@@ -710,7 +718,7 @@ __global__ __launch_bounds__(256) void k_spconv_bf16(const float* __restrict__ X
   for (int e = t; e < BM * K; e += 256) {
     int r = e / K, k = e - r * K;
     int j = row0 + r, v = -1;
-    if (j < n_out) v = nbr ? nbr[(size_t)j * K + k] : (j < n_in ? j : -1);
+    if (j < n_out) v = nbr ? nbr[(size_t)j * K + (mirror ? K - 1 - k : k)] : (j < n_in ? j : -1);
     nbrS[e] = v;
     if (v >= 0) tapAny[k] = 1;
   }
@@ -970,7 +978,7 @@ __global__ __launch_bounds__(256, 3) void k_spconv_bf16_fast(const void* __restr
     const int* src = nbr ? nbr + (size_t)j * K : nullptr;
     for (int k = k0; k < k1; ++k) {
       int v = -1;
-      if (j < n_out) v = src ? src[k] : (j < n_in ? j : -1);
+      if (j < n_out) v = src ? src[(io & ES_IO_MIRROR) ? K - 1 - k : k] : (j < n_in ? j : -1);
       nbrS[r * K + k] = v;
       if (v >= 0) tapFlag[k] = 1;
     }
@@ -1234,7 +1242,7 @@ __global__ __launch_bounds__(256, (KB == 1 && NBUF == 2) ? 3 : 2) void k_spconv_
     const int* src = nbr ? nbr + (size_t)j * K : nullptr;
     for (int k = k0; k < k1; ++k) {
       int v = -1;
-      if (j < n_out) v = src ? src[k] : (j < n_in ? j : -1);
+      if (j < n_out) v = src ? src[(io & ES_IO_MIRROR) ? K - 1 - k : k] : (j < n_in ? j : -1);
       nbrS[r * K + k] = v;
       if (v >= 0) tapFlag[k] = 1;
     }
@@ -1987,7 +1995,10 @@ static int spconv_fwd_bf16_impl(const void* Xv, int x_is_bf16, int ldx, const vo
                                 int y_half = 0, int r_half = 0) {
   if (n_out <= 0 || Cout <= 0) return 0;
   if (K > MAXK) return -2;
-  int io = (y_half ? ES_IO_Y16 : 0) | ((r_half && ep_res) ? ES_IO_R16 : 0) | (y_half & 0xff00);   // (bits 8-15: dev ablation switches of k_rowgemm2_bf16, tools/bench_rowgemm.py)
+  const int mirror = accumulate & 2;                                   // bit 1: mirrored tap walk (ES_IO_MIRROR)
+  accumulate &= 1;
+  if (mirror && (!(K & 1) || nbr == nullptr)) return -3;
+  int io = (mirror ? ES_IO_MIRROR : 0) | (y_half ? ES_IO_Y16 : 0) | ((r_half && ep_res) ? ES_IO_R16 : 0) | (y_half & 0xff00);   // (bits 8-15: dev ablation switches of k_rowgemm2_bf16, tools/bench_rowgemm.py)
   if (y_half && (accumulate || (ldy % 4) || (Cout % 4) || (((uintptr_t)Y) & 7))) return -7;   // bf16 rows: 8-byte stores
   if ((io & ES_IO_R16) && ((ep_ldr % 4) || (((uintptr_t)ep_res) & 7))) return -7;
   hipStream_t st = (hipStream_t)stream;

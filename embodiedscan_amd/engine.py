@@ -584,6 +584,13 @@ def _use_shadow(n_rows, C, K, cin, cout):
 HALO = [os.environ.get('ES_HALO', '1') != '0']
 if os.environ.get('ES_HALO_MIN_WGS') is not None:
     hip.raw('es_halo_set_option')(30, int(os.environ['ES_HALO_MIN_WGS']))
+if os.environ.get('ES_HALO_PLAN_BITMAP') is not None:       # A/B switch of the bitmap halo plan (default: on; 0: hash-and-rank)
+    hip.raw('es_halo_set_option')(32, int(os.environ['ES_HALO_PLAN_BITMAP']))
+
+
+def _is_mirror(inv):
+    """inv is a sparse.MirrorInv handle: "the inverse map is the forward map inv.nbr with its taps mirrored" (no inverse map tensor exists)"""
+    return inv is not None and not isinstance(inv, torch.Tensor)
 
 
 def _halo_ok(nbr, n_out, n_in, ldx, K, cin, cout):
@@ -612,7 +619,7 @@ def halo_plan(nbr):
 def _halo_launch(Xh, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc):
     """nbr: the launch's gather map.  The INVERSE map of a stride-1 convolution on one coordinate set is its forward map with the
     taps mirrored (sparse.CoordSet.inverse_map marks it `_mirror_of`): such a data gradient runs on the forward map's plan."""
-    fwd = getattr(nbr, '_mirror_of', None)
+    fwd = nbr.nbr if _is_mirror(nbr) else getattr(nbr, '_mirror_of', None)
     loc, hrows, hcnt = halo_plan(fwd if fwd is not None else nbr)
     return hip.try_call('es_spconv_halo_bf16', Xh, ldx, Wp, P(loc), P(hrows), P(hcnt), n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc,
                         int(fwd is not None), _stream())
@@ -853,6 +860,8 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
                 and hip.try_call('es_img_dgrad3_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, P(gate), P(x.d),
                                  _ld(x.d), P(x.g), _ld(x.g), s)):
             return
+        if _is_mirror(inv):                      # the fused-epilogue entry points have no mirrored tap walk: the real inverse map
+            inv = inv.real()
         if x.d.dtype == torch.bfloat16:          # the gate operand is the bf16 activation (only its sign is read)
             call('es_spconv_fwd_bf16_io', P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
                  P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
@@ -875,6 +884,8 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
     if gh is not None and _halo_ok(inv, n_in, n_out, cout, K, cout, cin) and \
             _halo_launch(P(gh), cout, P(w.bf16()[0]), inv, n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc):
         return
+    if _is_mirror(inv):                          # gather kernels on the forward map, taps mirrored (bit 1 of `accumulate`): same bits as on
+        inv, acc = inv.nbr, acc | 2              # the inverse map, which is never built
     if gh is not None:
         _fwd_bf16(P(gh), 1, cout, P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gh)
     elif bf and cout >= 16:

@@ -63,6 +63,8 @@ for _key, _env in ((4, 'ES_WG_BIG_TARGET'), (5, 'ES_WG_BIG_ROWS'), (6, 'ES_WG_SM
                   (16, 'ES_SPLIT_FOLD'), (19, 'ES_RG128_MIN_WGS'), (20, 'ES_WSHARE'), (21, 'ES_NARROW'), (23, 'ES_RG320'), (24, 'ES_LIN_SMALL'), (25, 'ES_EXPAND'), (26, 'ES_EXPAND_WGS')):
     if os.environ.get(_env) is not None:
         _fn['es_set_option'](_key, int(os.environ[_env]))
+if os.environ.get('ES_FOCAL_INFLIGHT') is not None:    # A/B switch of the focal-loss kernel with its loads in flight (default: on)
+    _fn['es_losses_set_option'](40, int(os.environ['ES_FOCAL_INFLIGHT']))
 
 
 class HipError(RuntimeError):

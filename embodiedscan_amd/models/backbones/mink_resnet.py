@@ -70,7 +70,7 @@ class MinkResNet:
                 cs.inverse_map(oc, k)
             cs = oc
             cs.kernel_map(cs, 3)                         # conv2 of every block, conv1 of the blocks behind the first
-            cs.inverse_map(cs, 3)
+            cs.self_inverse(3)                           # (with sparse.MIRROR_TAPS: no inverse map, the forward map mirrored)
 
     def forward(self, x):
         tr = self.training
@@ -95,12 +95,12 @@ class MinkResNet:
                     idt = blk['down'][1](idt, act=0, training=tr)
                     cs = oc
                 else:
-                    o = E.conv(f, blk['conv1'], cs.kernel_map(cs, 3), cs.inverse_map(cs, 3), cs.n)
+                    o = E.conv(f, blk['conv1'], cs.kernel_map(cs, 3), cs.self_inverse(3), cs.n)
                     idt = f
                 c1 = o
                 o = blk['norm1'](o, act=1, training=tr)
                 n1 = o
-                o = E.conv(o, blk['conv2'], cs.kernel_map(cs, 3), cs.inverse_map(cs, 3), cs.n)
+                o = E.conv(o, blk['conv2'], cs.kernel_map(cs, 3), cs.self_inverse(3), cs.n)
                 f = blk['norm2'](o, act=1, res=idt, training=tr)       # relu(bn(conv2) + identity)
                 if self.trace is not None:
                     self.trace += [c1, n1, o, f]

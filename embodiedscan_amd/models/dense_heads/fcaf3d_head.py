@@ -103,7 +103,7 @@ class _BN:
 def conv3(st, w, out_set=None):
     """3^3 MinkowskiConvolution on the same coordinate set."""
     cs = st.cs
-    nbr, inv = cs.kernel_map(cs, 3), cs.inverse_map(cs, 3)
+    nbr, inv = cs.kernel_map(cs, 3), cs.self_inverse(3)
     return SparseTensor(cs, E.conv(st.F, w, nbr, inv, cs.n))
 
 
@@ -185,17 +185,17 @@ class FCAF3DHeadRotMat:
         x = level_sets[-1]
         thr = self.pts_prune_threshold
         if maps:                                        # next-batch prefetch: the 3^3 maps of the out_block convolutions too
-            x.kernel_map(x, 3), x.inverse_map(x, 3)
+            x.kernel_map(x, 3), x.self_inverse(3)
         for i in range(len(level_sets) - 2, -1, -1):
             c = x.children()
             if maps:                                    # up_block's 3^3 convolution runs on the generated children
-                c.kernel_map(c, 3), c.inverse_map(c, 3)
+                c.kernel_map(c, 3), c.self_inverse(3)
             u, _, _ = sparse.union(c, level_sets[i])          # (generated children first: see _levels)
             off = u.offsets()
             if any(off[b + 1] - off[b] > thr for b in range(u.n_batch)):
                 break                                   # pruning is live: the set the out_block sees depends on scores
             if maps:
-                u.kernel_map(u, 3), u.inverse_map(u, 3)
+                u.kernel_map(u, 3), u.self_inverse(3)
             x = u
 
     def _levels(self, inputs):

@@ -58,17 +58,17 @@ class MinkNeck:
         x = level_sets[-1]
         thr = self.pts_prune_threshold
         if maps:
-            x.kernel_map(x, 3), x.inverse_map(x, 3)
+            x.kernel_map(x, 3), x.self_inverse(3)
         for i in range(len(level_sets) - 2, -1, -1):
             c = x.children()
             if maps:
-                c.kernel_map(c, 3), c.inverse_map(c, 3)
+                c.kernel_map(c, 3), c.self_inverse(3)
             u, _, _ = sparse.union(c, level_sets[i])          # (generated children first: see _levels)
             off = u.offsets()
             if any(off[b + 1] - off[b] > thr for b in range(u.n_batch)):
                 break
             if maps:
-                u.kernel_map(u, 3), u.inverse_map(u, 3)
+                u.kernel_map(u, 3), u.self_inverse(3)
             x = u
 
     def levels(self, inputs):

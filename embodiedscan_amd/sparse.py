@@ -7,6 +7,7 @@ embodiedscan/models/detectors/sparse_featfusion_single_stage.py:215-218): every 
 derived from one input shares the maps cached here.
 """
 import ctypes
+import os
 import weakref
 
 import torch
@@ -141,6 +142,13 @@ class CoordSet:
             self.cache[key] = (hip.register_map(inv), weakref.ref(out))
         return inv
 
+    def self_inverse(self, ksize):
+        """what a stride-1 convolution on this set hands engine.conv() as its inverse map: with MIRROR_TAPS a MirrorInv handle on the
+        forward map (no es_inverse_map launch, no second map tensor), otherwise inverse_map(self, ksize)"""
+        if MIRROR_TAPS[0] and ksize % 2 == 1:
+            return MirrorInv(self, ksize, self.kernel_map(self, ksize))
+        return self.inverse_map(self, ksize)
+
     def children(self):
         """MinkowskiGenerativeConvolutionTranspose(k=2,s=2) output set: row 8*i+k."""
         if 'gen' not in self.cache:
@@ -148,6 +156,25 @@ class CoordSet:
             call('es_gen_children_keys', P(self.keys), self.n, self.ts // 2, P(keys), _stream())
             self.cache['gen'] = CoordSet(keys, self.n * 8, self.ts // 2, self.n_batch)
         return self.cache['gen']
+
+
+# A set's own odd-kernel inverse map is its forward map with the taps mirrored (inverse_map above), and every data-gradient kernel can
+# walk the forward map that way (the halo kernel's `mirror`, bit 1 of the gather entry points' `accumulate`): such maps are not built.
+# ES_MIRROR_TAPS=0 is the A/B switch and the way back: self_inverse() then returns the real inverse map and every launch is the old one.
+MIRROR_TAPS = [os.environ.get('ES_MIRROR_TAPS', '1') != '0']
+
+
+class MirrorInv:
+    """stands in for CoordSet.inverse_map(cs, ksize) of a set's own odd-kernel map: `nbr` is the forward map, to be walked with mirrored
+    taps; real() builds (and caches on the set) the inverse map itself, for a launch that cannot mirror.  Not cached on the set (it refers
+    to it: a cycle); made per call, it lives as long as the convolution's tape entry."""
+    __slots__ = ('cs', 'ksize', 'nbr')
+
+    def __init__(self, cs, ksize, nbr):
+        self.cs, self.ksize, self.nbr = cs, ksize, nbr
+
+    def real(self):
+        return self.cs.inverse_map(self.cs, self.ksize)
 
 
 COORD_BATCH = [__import__('os').environ.get('ES_COORD_BATCH', '1') != '0']

@@ -110,7 +110,11 @@ int es_compact_mask(const int64_t* keys, int n, const int* mask, int* scratch, i
 /* ---- convolution engine (replaces MinkowskiConvolution*, and conv2d through image-grid maps) ------ */
 /* Y[j] (+)= sum_k X[nbr[j,k]] . W[k] (+ bias).  W is [K][Cin][Cout]; trans_w: W is [K][Cout][Cin] (dgrad).
  * nbr == NULL means the identity map with K == 1 (plain row GEMM).  mink_resnet.py:58-62,88-120;
- * fcaf3d_head.py:907-984,1116-1136 */
+ * fcaf3d_head.py:907-984,1116-1136
+ * `accumulate` of es_spconv_fwd, es_spconv_fwd_bf16 and es_spconv_fwd_bf16_ws is a bit set: bit 0 = add to Y, bit 1 = MIRRORED TAP WALK:
+ * tap k of row j gathers X[nbr[j, K - 1 - k]].  A coordinate set's own odd-kernel map read this way IS its inverse map
+ * (inv[i][k] == nbr[i][K - 1 - k]), so a stride-1 data gradient runs on the forward map and no inverse map is built; only the staging of
+ * the map tile differs, the output bits equal a launch on the real inverse map.  -3: bit 1 with an even K or nbr == NULL. */
 int es_spconv_fwd(const float* X, int ldx, const float* W, const int* nbr, int n_out, int n_in, int K, int Cin,
                   int Cout, const float* bias, float* Y, int ldy, int trans_w, int accumulate, void* stream);
 /* bf16-MFMA variant (f32 features rounded to bf16 while staged, f32 accumulate).  W_bf16 is [K][Cout][Cin]
@@ -373,6 +377,9 @@ int es_focal_loss(const float* logits, int ldl, const int* labels, int N, int C,
 int es_focal_loss_clear(const float* logits, int ldl, const int* labels, int N, int C, float gamma, float alpha,
                         const float* avg_factor_dev, float grad_scale, float* grad, int ldg, double* partial /* 2048 */,
                         float* loss_out /* accumulated */, int lead, int tail, void* stream);
+/* key 40: 1 (default) = rows of at most 320 classes run with two rows of loads in flight per wave (k_focal_inflight, bit-identical to
+ * k_focal); 0 = k_focal for every C.  -2: unknown key. */
+int es_losses_set_option(int key, int value);
 /* bbox[:, :6] = clamp(exp(scale * reg[:, :6]), 1e-3), bbox[:, 6:] = reg[:, 6:]  (fcaf3d_head.py:1135-1137) */
 int es_reg_decode_fwd(const float* reg, int ldr, int n, const float* scale, float* bbox /* (n,12) */, void* stream);
 /* partial: >= 512 floats of scratch (the Scale gradient is reduced in a fixed order, no atomics) */
@@ -700,6 +707,9 @@ int es_dconv_set_option(int key, int value);
  * es_halo_plan: from a kernel map nbr[n_out][27] (es_kernel_map / es_inverse_map) -> loc[rows][27] uint16 (position of the
  *   neighbour in its tile's halo list, 0xFFFF absent), hrows[tiles][256*27] int32 (the tile's sorted distinct source rows),
  *   hcnt[tiles]; rows = es_halo_plan_rows(n_out) (whole tiles), tiles = rows / 256.  Cached with the map by the caller.
+ *   es_halo_set_option 32 (default 1): tiles whose present entries span at most 2^19 source rows are planned by an LDS bitmap (mark,
+ *   popcount, scan) instead of the hash-and-rank code; 0: hash-and-rank for every tile.  Same loc / hcnt / hrows[0 .. hcnt) either way;
+ *   hrows past hcnt is unspecified.
  * es_spconv_halo_bf16: Y (n_out x ldy, f32) (+)= conv of the bf16 rows Xh (n_in x ldx) with W_bf16 = the [27][Cout][Cin] copy
  *   (forward) or the natural [27][Cin][Cout] copy with the roles of Cin / Cout swapped and the plan of the inverse map (data
  *   gradient).  Cin % 64, Cout % 128, ldx % 8; -4 otherwise.  A tile whose halo exceeds the 704 resident rows runs in pages
