@@ -202,3 +202,299 @@ extern "C" int es_nms3d_multiclass(const float* boxes, const float* scores, int 
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------ overlays on the recording's frames
+// Predictions drawn onto the u8 frames the model consumed: 9-DoF boxes (es_render_project + es_render_boxes) and an occupancy
+// volume (es_render_occupancy).  Every decision is int32 / int64 arithmetic or plain f64 (+ - * / floor, compares; no FMA
+// contraction in this build), there are no atomics and no f32 arithmetic: tests/render_spec.py restates each kernel and the
+// output is held to it byte for byte.  The only library calls are the six f64 cos / sin of a box's Euler angles; the spec keeps
+// every projected coordinate 1e-6 away from a rounding boundary, which absorbs their last-bit differences.
+#define RND_TW 64                  // a workgroup owns RND_TH rows of RND_TW pixels: one wave per row, 192 contiguous bytes per row
+#define RND_TH 4
+#define RND_CHUNK 64               // box records staged through LDS per round: one lane of wave 0 per record
+#define RND_MAX 4096               // H, W and the guard band |u|, |v| <= RND_MAX
+#define RND_SKIP 256               // mask bit: the camera centre lies inside the box
+
+// Box i seen from view v -> rec[(v*n + i)*ES_RENDER_REC ...] (layout: include/es_hip.h).  Operation order, all f64:
+//   half = dims * 0.5;  R = Rz(a) Rx(b) Ry(g) as make_box of ground.hip (columns = the box axes)
+//   C_j  = -((E[0][j]*E[0][3] + E[1][j]*E[1][3]) + E[2][j]*E[2][3]);  d = C - centre;  loc_j = (R[0][j]*d0 + R[1][j]*d1) + R[2][j]*d2
+//   skip = |loc_j| <= half_j for j = 0, 1, 2
+//   corner c: l_a = bit a of c ? half_a : -half_a;  X_i = centre_i + ((R[i][0]*l0 + R[i][1]*l1) + R[i][2]*l2)
+//   cam_i = ((E[i][0]*X0 + E[i][1]*X1) + E[i][2]*X2) + E[i][3];  z = cam_2
+//   p_r = ((K[r][0]*cam0 + K[r][1]*cam1) + K[r][2]*cam2) + K[r][3] for r = 0, 1;  u = p_0 / z, v = p_1 / z  (only where z >= 1e-4)
+//   usable = z >= 1e-4 and -4096 <= u <= 4096 and -4096 <= v <= 4096;  q = (int)floor(4*u + 0.5), (int)floor(4*v + 0.5), else 0, 0
+__global__ void k_render_project(const float* __restrict__ boxes, int n, const float* __restrict__ ext,
+                                 const float* __restrict__ intr, int V, int* __restrict__ rec) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= V * n) return;
+  const int v = t / n, i = t - v * n;
+  const float* b = boxes + (size_t)i * 9;
+  const float* E = ext + (size_t)v * 16;
+  const float* K = intr + (size_t)v * 16;
+  const double c[3] = {b[0], b[1], b[2]};
+  const double h[3] = {(double)b[3] * 0.5, (double)b[4] * 0.5, (double)b[5] * 0.5};
+  const double ca = cos((double)b[6]), sa = sin((double)b[6]), cb = cos((double)b[7]), sb = sin((double)b[7]);
+  const double cc = cos((double)b[8]), sc = sin((double)b[8]);
+  const double R[3][3] = {{ca * cc - sa * sb * sc, -(sa * cb), ca * sc + sa * sb * cc},
+                          {sa * cc + ca * sb * sc, ca * cb, sa * sc - ca * sb * cc},
+                          {-(cb * sc), sb, cb * cc}};
+  double e[3][4];
+  for (int r = 0; r < 3; ++r)
+    for (int k = 0; k < 4; ++k) e[r][k] = (double)E[r * 4 + k];
+  double d[3];
+  for (int j = 0; j < 3; ++j) d[j] = -((e[0][j] * e[0][3] + e[1][j] * e[1][3]) + e[2][j] * e[2][3]) - c[j];
+  bool inside = true;
+  for (int j = 0; j < 3; ++j) {
+    const double loc = (R[0][j] * d[0] + R[1][j] * d[1]) + R[2][j] * d[2];
+    inside = inside && (loc <= h[j]) && (loc >= -h[j]);
+  }
+  int* o = rec + (size_t)t * ES_RENDER_REC;
+  int mask = inside ? RND_SKIP : 0;
+  int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = -0x7fffffff - 1, by1 = -0x7fffffff - 1;
+  for (int k = 0; k < 8; ++k) {
+    const double l0 = (k & 1) ? h[0] : -h[0], l1 = (k & 2) ? h[1] : -h[1], l2 = (k & 4) ? h[2] : -h[2];
+    double X[3], cam[3];
+    for (int r = 0; r < 3; ++r) X[r] = c[r] + ((R[r][0] * l0 + R[r][1] * l1) + R[r][2] * l2);
+    for (int r = 0; r < 3; ++r) cam[r] = ((e[r][0] * X[0] + e[r][1] * X[1]) + e[r][2] * X[2]) + e[r][3];
+    const double z = cam[2];
+    int qx = 0, qy = 0;
+    if (z >= 1e-4) {
+      const double u = (((double)K[0] * cam[0] + (double)K[1] * cam[1]) + (double)K[2] * cam[2] + (double)K[3]) / z;
+      const double w = (((double)K[4] * cam[0] + (double)K[5] * cam[1]) + (double)K[6] * cam[2] + (double)K[7]) / z;
+      if (u <= (double)RND_MAX && u >= -(double)RND_MAX && w <= (double)RND_MAX && w >= -(double)RND_MAX) {
+        qx = (int)floor(4.0 * u + 0.5);
+        qy = (int)floor(4.0 * w + 0.5);
+        mask |= 1 << k;
+        bx0 = min(bx0, qx); bx1 = max(bx1, qx); by0 = min(by0, qy); by1 = max(by1, qy);
+      }
+    }
+    o[2 * k] = qx;
+    o[2 * k + 1] = qy;
+  }
+  o[16] = mask;
+  o[17] = bx0; o[18] = by0; o[19] = bx1; o[20] = by1;
+  o[21] = 0; o[22] = 0; o[23] = 0;
+}
+
+// (byte loads / stores on purpose: the 192-byte row of a wave moved as 48 dwords with lane shuffles measured SLOWER)
+__device__ inline void rnd_load(const unsigned char* src, int chw, int v, int H, int W, int y, int x, int& r, int& g, int& b) {
+  if (chw) {
+    const size_t pl = (size_t)H * W, p = (size_t)v * 3 * pl + (size_t)y * W + x;
+    r = src[p]; g = src[p + pl]; b = src[p + 2 * pl];
+  } else {
+    const size_t p = (((size_t)v * H + y) * W + x) * 3;
+    r = src[p]; g = src[p + 1]; b = src[p + 2];
+  }
+}
+__device__ inline void rnd_store(unsigned char* dst, int v, int H, int W, int y, int x, int r, int g, int b) {
+  const size_t p = (((size_t)v * H + y) * W + x) * 3;
+  dst[p] = (unsigned char)r; dst[p + 1] = (unsigned char)g; dst[p + 2] = (unsigned char)b;
+}
+__device__ inline int rnd_blend(int c, int col, int alpha) { return (c * alpha + col * (256 - alpha) + 128) >> 8; }
+
+// edge (lo, a): from corner lo (bit a clear) to lo | 1 << a; its slot = a * 4 + (lo with bit a squeezed out)
+__host__ __device__ constexpr int rnd_edge(int lo, int a) { return a * 4 + (a == 0 ? lo >> 1 : a == 1 ? ((lo & 1) | ((lo >> 2) << 1)) : (lo & 3)); }
+
+// Pixel (x, y) has the centre (px, py) = (4x + 2, 4y + 2) in quarter-pixels.  Boxes in ascending row order; for box i:
+//   edge (A -> B drawable: both ends usable): d = B - A, e = P - A, cross = d.x*e.y - d.y*e.x, dot = d.x*e.x + d.y*e.y, len2 = d.d (int64)
+//     near = dot <= 0 ? e.e <= r^2 : dot >= len2 ? (e - d).(e - d) <= r^2 : cross^2 <= r^2 * len2        (len2 = 0: the disc round A)
+//   face (fixed axis a at s, other axes b < c; P0 = s << a, P1 = P0 | 1 << b, P2 = P1 | 1 << c, P3 = P0 | 1 << c; all four usable):
+//     f0 = cross(P0 -> P1), f1 = cross(P1 -> P2), f2 = cross(P2 -> P3) = -cross(P3 -> P2), f3 = cross(P3 -> P0) = -cross(P0 -> P3)
+//     covered = (all f >= 0 or all f <= 0) and not all f == 0
+//   any edge near: c = colour_i;  else any face covered: c = (c*alpha + colour_i*(256 - alpha) + 128) >> 8 per channel
+// A record whose rectangle (grown by radius_q) misses the tile's pixel centres, or with the skip bit, or with no usable corner, is
+// dropped by wave 0's ballot before the pixel loop -- a face lies inside the rectangle of its corners and a near edge inside the
+// grown one, so the cull changes no byte -- and the surviving records keep their order.
+__global__ __launch_bounds__(RND_TW * RND_TH) void k_render_boxes(const unsigned char* src, int chw, int H, int W,
+                                                                  const int* __restrict__ rec, const unsigned char* __restrict__ colors,
+                                                                  int n, int radius_q, int alpha, unsigned char* dst /* may be src */) {
+  __shared__ int s_rec[RND_CHUNK][18];            // 16 coordinates, the usable mask, the colour
+  __shared__ int s_cnt;
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  const int v = blockIdx.z, x0 = blockIdx.x * RND_TW, y0 = blockIdx.y * RND_TH;
+  const int x = x0 + lane, y = y0 + row;
+  const bool live = x < W && y < H;
+  int cr = 0, cg = 0, cbl = 0;
+  if (live) rnd_load(src, chw, v, H, W, y, x, cr, cg, cbl);
+  const int px = 4 * x + 2, py = 4 * y + 2;
+  const int tx0 = 4 * x0 + 2, tx1 = 4 * min(x0 + RND_TW - 1, W - 1) + 2, ty0 = 4 * y0 + 2, ty1 = 4 * min(y0 + RND_TH - 1, H - 1) + 2;
+  const long long r2 = (long long)radius_q * radius_q;
+  for (int base = 0; base < n; base += RND_CHUNK) {
+    __syncthreads();                              // the previous round's readers are done with s_rec
+    if (row == 0) {
+      const int i = base + lane;
+      const int* rc = rec + ((size_t)v * n + min(i, n - 1)) * ES_RENDER_REC;
+      bool keep = false;
+      if (i < n) {
+        const int m = rc[16];
+        keep = !(m & RND_SKIP) && (m & 255) && rc[17] - radius_q <= tx1 && rc[19] + radius_q >= tx0 && rc[18] - radius_q <= ty1 &&
+               rc[20] + radius_q >= ty0;
+      }
+      const unsigned long long bal = __ballot(keep);
+      if (keep) {
+        const int k = __popcll(bal & ((1ull << lane) - 1ull));
+        for (int j = 0; j < 17; ++j) s_rec[k][j] = rc[j];
+        s_rec[k][17] = (int)colors[(size_t)i * 3] | ((int)colors[(size_t)i * 3 + 1] << 8) | ((int)colors[(size_t)i * 3 + 2] << 16);
+      }
+      if (lane == 0) s_cnt = __popcll(bal);
+    }
+    __syncthreads();
+    const int cnt = s_cnt;
+    for (int k = 0; k < cnt; ++k) {               // uniform over the workgroup: every branch on the mask below is too
+      const int* q = s_rec[k];
+      const int m = q[16];
+      long long cross[12];
+      bool near = false, covered = false;
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int lo = 0; lo < 8; ++lo) {
+          if (lo & (1 << a)) continue;
+          const int hi = lo | (1 << a), e = rnd_edge(lo, a);
+          cross[e] = 0;
+          if ((m >> lo) & (m >> hi) & 1) {
+            const int ax = q[2 * lo], ay = q[2 * lo + 1];
+            const int dx = q[2 * hi] - ax, dy = q[2 * hi + 1] - ay, ex = px - ax, ey = py - ay;
+            const long long c = (long long)dx * ey - (long long)dy * ex;
+            const long long dot = (long long)dx * ex + (long long)dy * ey, len2 = (long long)dx * dx + (long long)dy * dy;
+            const int fx = ex - dx, fy = ey - dy;
+            const bool hit = dot <= 0 ? ((long long)ex * ex + (long long)ey * ey <= r2)
+                                      : dot >= len2 ? ((long long)fx * fx + (long long)fy * fy <= r2) : (c * c <= r2 * len2);
+            cross[e] = c;
+            near = near || hit;
+          }
+        }
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int bb = a == 0 ? 1 : 0, cx = a == 2 ? 1 : 2;
+          const int p0 = s << a, p1 = p0 | (1 << bb), p2 = p1 | (1 << cx), p3 = p0 | (1 << cx);
+          const int fm = (1 << p0) | (1 << p1) | (1 << p2) | (1 << p3);
+          if ((m & fm) == fm) {
+            const long long f0 = cross[rnd_edge(p0, bb)], f1 = cross[rnd_edge(p1, cx)], f2 = -cross[rnd_edge(p3, bb)],
+                            f3 = -cross[rnd_edge(p0, cx)];
+            const bool in = ((f0 >= 0 && f1 >= 0 && f2 >= 0 && f3 >= 0) || (f0 <= 0 && f1 <= 0 && f2 <= 0 && f3 <= 0)) &&
+                            (f0 | f1 | f2 | f3) != 0;
+            covered = covered || in;
+          }
+        }
+      const int col = q[17], r = col & 255, g = (col >> 8) & 255, b = (col >> 16) & 255;
+      if (near) { cr = r; cg = g; cbl = b; }
+      else if (covered) { cr = rnd_blend(cr, r, alpha); cg = rnd_blend(cg, g, alpha); cbl = rnd_blend(cbl, b, alpha); }
+    }
+  }
+  if (live) rnd_store(dst, v, H, W, y, x, cr, cg, cbl);
+}
+
+struct RndGrid { double rmin[3], size[3]; int n[3]; };
+// One thread per pixel, f64 with + - * / floor and compares only.  M = rays[v][0..8] (row-major R^T K^-1), o = rays[v][9..11]:
+//   d_i = (M[i][0]*(x + 0.5) + M[i][1]*(y + 0.5)) + M[i][2]
+//   slab: tmin = 0, tmax = +inf, axis = 0; for i = 0, 1, 2: lo = rmin_i, hi = rmin_i + n_i*size_i;
+//     d_i == 0: miss unless lo <= o_i < hi;  else t0 = (lo - o_i)/d_i, t1 = (hi - o_i)/d_i, swapped if t0 > t1;
+//     t0 > tmin: tmin = t0, axis = i;  t1 < tmax: tmax = t1.          miss if tmin > tmax
+//   entry: idx_i = clamp((int)floor(((o_i + tmin*d_i) - rmin_i) / size_i), 0, n_i - 1)
+//   step_i = d_i > 0 ? 1 : d_i < 0 ? -1 : 0;  tnext_i = d_i == 0 ? +inf : ((rmin_i + (idx_i + (d_i > 0 ? 1 : 0))*size_i) - o_i)/d_i
+//   dt_i = d_i == 0 ? +inf : size_i / (d_i > 0 ? d_i : -d_i)
+//   at most X + Y + Z times: label = occ[idx]; 1 <= label < C: hit.  a = (tnext_0 <= tnext_1 and tnext_0 <= tnext_2) ? 0 :
+//     tnext_1 <= tnext_2 ? 1 : 2;  idx_a += step_a; outside 0 .. n_a - 1: miss;  tnext_a += dt_a;  axis = a
+//   hit: col = (palette[label] * shade[axis]) >> 8, shade = {256, 208, 160};  c = (c*alpha + col*(256 - alpha) + 128) >> 8
+__global__ __launch_bounds__(RND_TW * RND_TH) void k_render_occupancy(const unsigned char* src, int chw, int H, int W,
+                                                                      const double* __restrict__ rays, const unsigned char* __restrict__ occ,
+                                                                      RndGrid G, const unsigned char* __restrict__ palette, int C, int alpha,
+                                                                      unsigned char* dst /* may be src */) {
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  const int v = blockIdx.z, x = blockIdx.x * RND_TW + lane, y = blockIdx.y * RND_TH + row;
+  if (x >= W || y >= H) return;
+  int cr, cg, cbl;
+  rnd_load(src, chw, v, H, W, y, x, cr, cg, cbl);
+  const double* M = rays + (size_t)v * 12;
+  const double fx = (double)x + 0.5, fy = (double)y + 0.5, inf = __builtin_inf();
+  double d[3], o[3];
+  for (int i = 0; i < 3; ++i) { d[i] = (M[i * 3] * fx + M[i * 3 + 1] * fy) + M[i * 3 + 2]; o[i] = M[9 + i]; }
+  double tmin = 0.0, tmax = inf;
+  int axis = 0;
+  bool miss = false;
+  for (int i = 0; i < 3; ++i) {
+    const double lo = G.rmin[i], hi = G.rmin[i] + (double)G.n[i] * G.size[i];
+    if (d[i] == 0.0) {
+      if (!(o[i] >= lo && o[i] < hi)) miss = true;
+    } else {
+      double t0 = (lo - o[i]) / d[i], t1 = (hi - o[i]) / d[i];
+      if (t0 > t1) { const double s = t0; t0 = t1; t1 = s; }
+      if (t0 > tmin) { tmin = t0; axis = i; }
+      if (t1 < tmax) tmax = t1;
+    }
+  }
+  if (!(tmin <= tmax)) miss = true;
+  int label = 0;
+  if (!miss) {
+    int idx[3], step[3];
+    double tnext[3], dt[3];
+    for (int i = 0; i < 3; ++i) {
+      int k = (int)floor(((o[i] + tmin * d[i]) - G.rmin[i]) / G.size[i]);
+      k = k < 0 ? 0 : k > G.n[i] - 1 ? G.n[i] - 1 : k;
+      idx[i] = k;
+      step[i] = d[i] > 0.0 ? 1 : d[i] < 0.0 ? -1 : 0;
+      tnext[i] = d[i] == 0.0 ? inf : ((G.rmin[i] + (double)(k + (d[i] > 0.0 ? 1 : 0)) * G.size[i]) - o[i]) / d[i];
+      dt[i] = d[i] == 0.0 ? inf : G.size[i] / (d[i] > 0.0 ? d[i] : -d[i]);
+    }
+    const int steps = G.n[0] + G.n[1] + G.n[2];
+    for (int s = 0; s < steps; ++s) {
+      const int l = occ[((size_t)idx[0] * G.n[1] + idx[1]) * G.n[2] + idx[2]];
+      if (l >= 1 && l < C) { label = l; break; }
+      const int a = (tnext[0] <= tnext[1] && tnext[0] <= tnext[2]) ? 0 : (tnext[1] <= tnext[2]) ? 1 : 2;
+      const int k = (a == 0 ? idx[0] : a == 1 ? idx[1] : idx[2]) + (a == 0 ? step[0] : a == 1 ? step[1] : step[2]);
+      if (k < 0 || k > (a == 0 ? G.n[0] : a == 1 ? G.n[1] : G.n[2]) - 1) break;
+      if (a == 0) { idx[0] = k; tnext[0] += dt[0]; } else if (a == 1) { idx[1] = k; tnext[1] += dt[1]; } else { idx[2] = k; tnext[2] += dt[2]; }
+      axis = a;
+    }
+  }
+  if (label) {
+    const int shade = axis == 0 ? 256 : axis == 1 ? 208 : 160;
+    cr = rnd_blend(cr, ((int)palette[label * 3] * shade) >> 8, alpha);
+    cg = rnd_blend(cg, ((int)palette[label * 3 + 1] * shade) >> 8, alpha);
+    cbl = rnd_blend(cbl, ((int)palette[label * 3 + 2] * shade) >> 8, alpha);
+  }
+  rnd_store(dst, v, H, W, y, x, cr, cg, cbl);
+}
+
+static inline bool rnd_frame_ok(int H, int W) { return H >= 1 && H <= RND_MAX && W >= 1 && W <= RND_MAX; }
+extern "C" int es_render_project(const float* boxes, int n, const float* extrinsic, const float* intrinsic, int V, int H, int W, int* rec,
+                                 void* stream) {
+  if (n < 0 || V < 0) return -5;
+  if (!rnd_frame_ok(H, W) || V > 65535 || (long long)V * n > (1ll << 30)) return -4;
+  if (n == 0 || V == 0) return 0;
+  hipLaunchKernelGGL(k_render_project, dim3(es_cdiv((long long)V * n, 64)), dim3(64), 0, (hipStream_t)stream, boxes, n, extrinsic,
+                     intrinsic, V, rec);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_render_boxes(const unsigned char* src, int chw, int V, int H, int W, const int* rec, const unsigned char* colors, int n,
+                               int radius_q, int alpha, unsigned char* dst, void* stream) {
+  if (n < 0 || V < 0) return -5;
+  if (!rnd_frame_ok(H, W) || V > 65535 || (long long)V * n > (1ll << 30) || radius_q < 1 || radius_q > 64 || alpha < 0 || alpha > 256 ||
+      (chw && (const void*)src == (const void*)dst))
+    return -4;
+  if (V == 0) return 0;
+  hipLaunchKernelGGL(k_render_boxes, dim3(es_cdiv(W, RND_TW), es_cdiv(H, RND_TH), V), dim3(RND_TW * RND_TH), 0, (hipStream_t)stream, src,
+                     chw, H, W, rec, colors, n, radius_q, alpha, dst);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_render_occupancy(const unsigned char* src, int chw, int V, int H, int W, const double* rays, const unsigned char* occ, int X,
+                                   int Y, int Z, const double* grid_host, const unsigned char* palette, int C, int alpha,
+                                   unsigned char* dst, void* stream) {
+  if (V < 0) return -5;
+  if (!rnd_frame_ok(H, W) || V > 65535 || alpha < 0 || alpha > 256 || C < 1 || C > 256 || X < 1 || Y < 1 || Z < 1 ||
+      (long long)X * Y * Z > (1ll << 30) || (chw && (const void*)src == (const void*)dst))
+    return -4;
+  if (V == 0) return 0;
+  RndGrid G;
+  for (int i = 0; i < 3; ++i) { G.rmin[i] = grid_host[i]; G.size[i] = grid_host[3 + i]; }
+  G.n[0] = X; G.n[1] = Y; G.n[2] = Z;
+  hipLaunchKernelGGL(k_render_occupancy, dim3(es_cdiv(W, RND_TW), es_cdiv(H, RND_TH), V), dim3(RND_TW * RND_TH), 0, (hipStream_t)stream,
+                     src, chw, H, W, rays, occ, G, palette, C, alpha, dst);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

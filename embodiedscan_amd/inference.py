@@ -1,6 +1,7 @@
-"""A posed RGB-D recording in, an object list (or an occupancy volume) out: the reference's demo (demo/demo.py) without the rendering.
+"""A posed RGB-D recording in, an object list (or an occupancy volume) out -- and, with --render, the prediction drawn onto the frames
+the model consumed: the reference's demo (demo/demo.py) without the 3-D viewer.
 
-    python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json]
+    python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json] [--render DIR]
 
 reads D/S/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}, runs the model of CONFIG in
 `predict` mode (or frame by frame through a walk session with --walk) and writes the filtered boxes, scores, labels and class names
@@ -10,7 +11,11 @@ filter_instances is the demo's nms_filter (demo.py:84-130) on the device: a scor
 true 9-DoF IoU and a per-class quota, in one launch of es_box3d_iou_filter behind es_topk_sorted.  It is not the head's NMS
 (bbox_head.predict: per class, BEV IoU, hundreds to thousands of boxes per prefix) and changes nothing there: everything here is opt-in.
 The IoU of a candidate row i with a kept row j is the [i][j] element of es_box3d_iou -- the candidate is the first argument -- and is
-compared in f32, like the score, against the f32 value of the threshold; a NaN IoU (zero-volume pair) does not suppress."""
+compared in f32, like the score, against the f32 value of the threshold; a NaN IoU (zero-volume pair) does not suppress.
+
+render=DIR (run_scene, walk_scene, --render): frame_0000.png ... = dscan['img'] -- the resized frames the image backbone saw -- under the
+prediction, projected with that sample's own depth2img matrices (frame_matrices), so the picture shows the projection the fusion used;
+legend.json (class name -> colour) lies next to them.  embodiedscan_amd.render draws on the device; with render=None nothing of it runs."""
 import json
 import os
 
@@ -185,26 +190,93 @@ def make_scene_batch(detector, dscan):
     return PL.make_batch([dscan])
 
 
+# ------------------------------------------------------------------------------------------------------------------ the picture
+def frame_matrices(dscan):
+    """-> (extrinsic, intrinsic), (V, 4, 4) f64 each: the scan's depth2img matrices at the resolution of dscan['img'] -- the fusion projects
+    with intrinsic @ extrinsic and then applies the resize's scale_factor (point_fusion.py:79-105); here the factor is folded into the
+    intrinsic's first two rows.  ValueError for a scan whose pipeline flipped / cropped the image or moved the cloud (a train-time
+    augmentation: its predictions do not live in the aligned frame)."""
+    meta = dscan['meta']
+    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
+    pm = meta[key]
+    E = np.stack([np.asarray(e, np.float64) for e in pm['extrinsic']])
+    intr = pm['intrinsic']
+    K = np.stack([np.asarray(k, np.float64) for k in intr]) if isinstance(intr, (list, tuple)) else np.repeat(np.asarray(intr, np.float64)[None], len(E), 0)
+    rot = np.asarray(meta.get('pcd_rotation', np.eye(3)), np.float64)
+    moved = (not np.array_equal(rot, np.eye(3)) or float(meta.get('pcd_scale_factor', 1.)) != 1. or bool(np.any(np.asarray(meta.get('pcd_trans', 0.)) != 0))
+             or meta.get('pcd_horizontal_flip', False) or meta.get('pcd_vertical_flip', False))
+    if moved or meta.get('flip', False) or tuple(meta.get('img_crop_offset', (0., 0.))) != (0., 0.):
+        raise ValueError('render: the pipeline augments the scan; draw on a test pipeline')
+    sx, sy = (float(s) for s in meta.get('scale_factor', (1., 1.)))
+    K = K.copy()
+    K[:, 0, :] *= sx
+    K[:, 1, :] *= sy
+    return E, K
+
+
+def _default_names(detector, kind):
+    nc = getattr(detector.bbox_head, 'num_classes', 0)
+    return [f'class_{i}' for i in range(nc)] if kind in ('det3d', 'cont-det3d') else ['empty'] + [f'class_{i}' for i in range(max(nc - 1, 0))]
+
+
+def scene_palette(detector):
+    """(n_classes, 3) u8: row l = the colour of label l.  Detectors skip render.class_palette's grey row 0; occupancy keeps it for `empty`"""
+    from . import render as RD
+    kind, nc = _kind(detector), int(getattr(detector.bbox_head, 'num_classes', 0))
+    return RD.class_palette(nc + 1)[1:] if kind in ('det3d', 'cont-det3d') else RD.class_palette(max(nc, 1))
+
+
+def draw_prediction(detector, frames, extrinsic, intrinsic, res, palette_dev):
+    """one prediction (InstanceData or an (X, Y, Z) volume) over frames (V, 3, H, W) u8 -> (V, H, W, 3) u8 on the device"""
+    from . import render as RD
+    if isinstance(res, InstanceData):
+        labels = res.labels_3d.long().clamp(0, palette_dev.shape[0] - 1)
+        return RD.render_boxes(frames, extrinsic, intrinsic, res.bboxes_3d, palette_dev[labels], layout='chw')
+    return RD.render_occupancy(frames, extrinsic, intrinsic, res, detector.point_cloud_range, palette_dev, layout='chw')
+
+
+def _write_legend(dir, detector, class_names):
+    kind = _kind(detector)
+    pal = scene_palette(detector)
+    names = list(class_names) if class_names is not None else _default_names(detector, kind)
+    names = names[:len(pal)] + [f'class_{i}' for i in range(len(names), len(pal))]
+    os.makedirs(dir, exist_ok=True)
+    with open(os.path.join(dir, 'legend.json'), 'w') as f:
+        json.dump({nm: [int(c) for c in pal[i]] for i, nm in enumerate(names)}, f)
+    return pal
+
+
 def _filtered(detector, inst, filter):
     if filter is None:
         return inst
     return filter_instances(inst, **dict(dict(n_classes=detector.bbox_head.num_classes), **filter))
 
 
-def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict()):
+def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None, class_names=None):
     """one `predict` over the folder.  Detectors: the filtered InstanceData per sample (the cont-det3d detector: one per prefix);
-    occupancy models: pred_occupancy per sample / prefix.  filter: keyword arguments of filter_instances; None: the raw prediction"""
+    occupancy models: pred_occupancy per sample / prefix.  filter: keyword arguments of filter_instances; None: the raw prediction.
+    render: a directory that receives every view of the scan under the final list / volume (the last prefix's for the continuous kinds)
+    as frame_0000.png ... and legend.json; None: nothing is drawn."""
     kind = _kind(detector)
-    data = detector.data_preprocessor(make_scene_batch(detector, load_scene(detector, scene_dir, pipeline, seed)), False)
+    dscan = load_scene(detector, scene_dir, pipeline, seed)
+    data = detector.data_preprocessor(make_scene_batch(detector, dscan), False)
     out = detector.forward(data['inputs'], data['data_samples'], mode='predict')
     if kind in ('occ', 'cont-occ'):
-        return [ds.pred_occupancy for ds in out]
-    return [_filtered(detector, ds.pred_instances_3d, filter) for ds in out]
+        res = [ds.pred_occupancy for ds in out]
+    else:
+        res = [_filtered(detector, ds.pred_instances_3d, filter) for ds in out]
+    if render is not None:
+        from . import render as RD
+        pal = torch.from_numpy(_write_legend(render, detector, class_names)).to(detector.device)
+        E, K = frame_matrices(dscan)
+        RD.save_frames(render, draw_prediction(detector, dscan['img'], E, K, res[-1], pal))
+    return res
 
 
-def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None):
-    """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene without the
-    rendering): opens a walk session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy)"""
+def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None):
+    """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene): opens a walk
+    session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy).  render: a directory that receives
+    frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn."""
     from . import pipeline as PL
     kind = _kind(detector)
     if kind not in ('cont-det3d', 'cont-occ'):
@@ -219,11 +291,18 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
     meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
     n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
     walk = detector.open_walk(meta, max_frames=max(n_frames, 1)) if kind == 'cont-det3d' else detector.open_walk(meta)
+    if render is not None:
+        from . import render as RD
+        pal = torch.from_numpy(_write_legend(render, detector, class_names)).to(detector.device)
+        E, K = frame_matrices(dscan)
     for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
         if t >= n_frames:
             break
         res = walk.observe(imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
-        yield t, (res if kind == 'cont-occ' else _filtered(detector, res, filter))
+        res = res if kind == 'cont-occ' else _filtered(detector, res, filter)
+        if render is not None:
+            RD.save_frames(render, draw_prediction(detector, dscan['img'][t:t + 1], E[t:t + 1], K[t:t + 1], res, pal), start=t)
+        yield t, res
 
 
 # ------------------------------------------------------------------------------------------------------------------ the command line
@@ -256,6 +335,7 @@ def main(argv=None):
     ap.add_argument('--score-thr', type=float, default=0.075)
     ap.add_argument('--topk-per-class', type=int, default=10)
     ap.add_argument('--out', default=None, help='JSON file (default: standard output)')
+    ap.add_argument('--render', default=None, metavar='DIR', help='write every frame under its prediction as DIR/frame_0000.png ... and DIR/legend.json')
     a = ap.parse_args(argv)
     det, cfg = init_model(a.config, a.checkpoint, a.device)
     scene_dir = os.path.join(a.root_dir, a.scene)
@@ -265,9 +345,9 @@ def main(argv=None):
     nc = getattr(det.bbox_head, 'num_classes', 0)
     names = _class_names(cfg, nc) if kind in ('det3d', 'cont-det3d') else ['empty'] + _class_names(cfg, max(nc - 1, 0))
     if a.walk:
-        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt)]
+        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names)]
     else:
-        results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt))]
+        results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names))]
     doc = json.dumps(dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt,
                           results=results))
     if a.out:

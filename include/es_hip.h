@@ -787,6 +787,38 @@ int es_img_dgrad1_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_im
                           int accumulate, void* stream);
 int es_img_stride_set_option(int key, int value);
 
+/* ---- overlays on the recording's frames (csrc/predict.hip) ------------------------------------------------------
+ * Frames: src u8, (V,3,H,W) with chw != 0 (what upload_scan leaves in dscan['img']) or (V,H,W,3); dst always (V,H,W,3); src == dst only
+ * with chw == 0.  extrinsic / intrinsic: the f32 (V,4,4) matrices of the fusion (depth2img: aligned frame -> camera, camera -> pixels) AT
+ * THE RESOLUTION OF THE FRAMES PASSED IN.  Pixel (x, y) covers [x, x+1) x [y, y+1); coordinates are kept in QUARTER-PIXELS, so its centre
+ * is (4x + 2, 4y + 2).  The exact operation order of all three kernels is written once at each kernel and restated by tests/render_spec.py.
+ * es_render_project: one thread per (view, box), f64 throughout.  rec[(v*n + i)*ES_RENDER_REC + ...]:
+ *   [2c], [2c+1]  q = floor(4u + 0.5), floor(4v + 0.5) of corner c = centre + R_ZXY (+-l/2, +-w/2, +-h/2), sign of axis a = + iff bit a of c
+ *                 (0, 0 for a corner that is not usable);
+ *   [16]          bits 0..7: corner c is USABLE = camera-space z >= 1e-4 and |u|, |v| <= 4096 -- the guard band: with |q| <= 2^14 and
+ *                 pixel centres below 2^14 every coordinate difference is below 2^15, an edge function (cross product) below 2^31 and
+ *                 its square below 2^62, so the rasteriser's products stay inside int64; bit 8: the camera centre (-R^T t of the
+ *                 extrinsic) lies inside the box (|local| <= dims/2 in the box's frame): the box is not drawn in this view;
+ *   [17..20]      min x, min y, max x, max y of the usable corners in quarter-pixels (min > max: none usable).  es_render_project does not
+ *                 know the line width: es_render_boxes grows the rectangle by its radius_q when it culls;   [21..23] 0.
+ * es_render_boxes: per pixel, the boxes in ascending row order; box i blends colour_i over the pixel (weight 256 - alpha; alpha = the
+ *   image's weight in 1/256) where the centre lies inside or on a face whose four corners are usable and sets colour_i where it lies
+ *   within radius_q quarter-pixels of an edge whose two ends are usable.  int32 / int64 only.  n = 0 copies / transposes src to dst.
+ *   The reference drawer's defaults: radius_q 4 (2 px thick), alpha 192.
+ * es_render_occupancy: per pixel, the ray through its centre (rays[v] = the 3x3 R^T K^-1, row-major, then the camera centre, f64, formed by
+ *   the caller) walks occ (X,Y,Z) u8 over [rmin, rmin + n*size] (grid_host: rmin[3], size[3], read on the HOST at the call); the first
+ *   voxel with 1 <= label < C blends palette[label] shaded {256, 208, 160}/256 by the axis of the face the ray entered through.
+ * Status: -5 for a negative count; -4, nothing written, for H or W outside 1 .. 4096, radius_q outside 1 .. 64, alpha outside 0 .. 256,
+ *   C outside 1 .. 256, a grid dimension < 1, V > 65535, src == dst with chw != 0.  n = 0 or V = 0 is not an error. */
+#define ES_RENDER_REC 24
+int es_render_project(const float* boxes /*(n,9)*/, int n, const float* extrinsic /*(V,4,4)*/, const float* intrinsic /*(V,4,4)*/,
+                      int V, int H, int W, int* rec /*(V,n,ES_RENDER_REC)*/, void* stream);
+int es_render_boxes(const unsigned char* src, int chw, int V, int H, int W, const int* rec, const unsigned char* colors /*(n,3)*/, int n,
+                    int radius_q, int alpha, unsigned char* dst /*(V,H,W,3)*/, void* stream);
+int es_render_occupancy(const unsigned char* src, int chw, int V, int H, int W, const double* rays /*(V,12)*/, const unsigned char* occ /*(X,Y,Z)*/,
+                        int X, int Y, int Z, const double* grid_host /*rmin[3], size[3]*/, const unsigned char* palette /*(C,3)*/, int C,
+                        int alpha, unsigned char* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
