@@ -165,6 +165,17 @@ class Tape:
 
 TAPE = Tape()
 
+
+class no_tape:
+    """with no_tape(): ... -- nothing is recorded on the tape; TAPE.enabled is restored on exit, exceptions included"""
+
+    def __enter__(self):
+        self.prev, TAPE.enabled = TAPE.enabled, False
+
+    def __exit__(self, *exc):
+        TAPE.enabled = self.prev
+
+
 # ------------------------------------------------------------------ captured launch sequences (hipGraph)
 # The image backbone's forward is ~65 launches with static shapes, static addresses and no host round trip, but queuing them
 # costs the host ~4 ms per step -- during which the point branch (whose kernels the image branch is meant to run under) has not

@@ -260,12 +260,8 @@ class FCAF3DHeadRotMat:
         from ...structures import EulerDepthInstance3DBoxes, InstanceData
         cfg = self.test_cfg or {}
         nms_pre, score_thr, iou_thr = cfg.get('nms_pre', 1000), cfg.get('score_thr', 0.01), cfg.get('iou_thr', 0.5)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False
-        try:
+        with E.no_tape():
             levels = self._levels(x)
-        finally:
-            E.TAPE.enabled = prev
         dev = levels[0]['ho'].d.device
         s = _stream()
         B = levels[0]['cs'].n_batch

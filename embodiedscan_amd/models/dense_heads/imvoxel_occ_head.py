@@ -33,12 +33,8 @@ class ImVoxelOccHead:
 
     def predict(self, x, batch_data_samples):
         """argmax over softmax of the finest level: (B, X, Y, Z) int64 (imvoxel_occ_head.py:93-108)"""
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False
-        try:
+        with E.no_tape():
             logits, dims = self.forward(x[:1])[0]
-        finally:
-            E.TAPE.enabled = prev
         return self.argmax(logits, dims)
 
     def argmax(self, logits, dims):

@@ -89,6 +89,7 @@ class DenseFusionOccPredictor(DetectorBase):
     def extract_feat(self, batch_inputs_dict, batch_data_samples):
         """dense_fusion_occ.py:120-259.  Returns [(Var (X_i*Y_i*Z_i, 128), (X_i, Y_i, Z_i))] fine -> coarse."""
         self._bind()
+        self.start_tape_parts()
         img = batch_inputs_dict['imgs']
         B, V = img.shape[:2]
         H, W = img.shape[-2:]

@@ -13,7 +13,6 @@ attribute, not a config key: the reference configuration builds unchanged) is th
 together; the 2-D features are computed once.  In eval mode every norm is per sample or folded, so the chunk size does not change
 the result."""
 import torch
-from ... import engine as E
 from ... import hip
 from ...hip import P, call
 from ...registry import MODELS
@@ -85,24 +84,19 @@ class Embodied3DDetector(SparseFeatureFusionSingleStage3DDetector):
         `predict_chunk` prefixes; the image backbone runs once."""
         T = self._check(batch_inputs_dict, batch_data_samples)
         chunk = max(1, int(self.predict_chunk))
-        was = self.training
-        self.train(False)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False
         results = []
-        try:
-            self._bind()
-            img_feats, V, hw, forked = self._image_feats(batch_inputs_dict['imgs'])
-            points = batch_inputs_dict['points']
-            for t0 in range(0, T, chunk):
-                t1 = min(T, t0 + chunk)
-                self._win_t0 = t0
-                x = self._fuse_points({'points': points[t0:t1]}, batch_data_samples[t0:t1], (img_feats, V, hw, forked and t0 == 0))
-                results += self.bbox_head.predict(x, batch_data_samples[t0:t1], **kwargs)
-        finally:
-            self._win_t0 = 0
-            E.TAPE.enabled = prev
-            self.train(was)
+        with self._predict_guard():
+            try:
+                self._bind()
+                img_feats, V, hw, forked = self._image_feats(batch_inputs_dict['imgs'])
+                points = batch_inputs_dict['points']
+                for t0 in range(0, T, chunk):
+                    t1 = min(T, t0 + chunk)
+                    self._win_t0 = t0
+                    x = self._fuse_points({'points': points[t0:t1]}, batch_data_samples[t0:t1], (img_feats, V, hw, forked and t0 == 0))
+                    results += self.bbox_head.predict(x, batch_data_samples[t0:t1], **kwargs)
+            finally:
+                self._win_t0 = 0
         for ds, r in zip(batch_data_samples, results):
             ds.pred_instances_3d = r
         return batch_data_samples

@@ -29,6 +29,7 @@ class EmbodiedOccPredictor(DenseFusionOccPredictor):
     def extract_feat(self, batch_inputs_dict, batch_data_samples):
         """embodied_occ.py:118-247.  Returns [(Var (T*X_i*Y_i*Z_i, 128), (X_i, Y_i, Z_i))] fine -> coarse, prefix-major rows."""
         self._bind()
+        self.start_tape_parts()
         img = batch_inputs_dict['imgs']
         B, V = img.shape[:2]
         H, W = img.shape[-2:]

@@ -3,12 +3,13 @@ kernels.  Same registry name, constructor arguments and forward(inputs, data_sam
 
 extract_feat is the mv-3ddet feature path (2-D / 3-D backbones + projection fusion, inherited) followed by MinkNeck;
 pre_decoder / forward_decoder / the head run on padded channels-last token matrices.  Text: see embodiedscan_amd/text.py."""
+import contextlib
 import os
 import torch
 from ... import engine as E
 from ... import hip
 from ...hip import P, call
-from ...params import ParamArena, grounder_specs
+from ...params import grounder_specs
 from ...registry import MODELS
 from ...text import HashTokenizer, HipTextEncoder, TextGraph, build_text_encoder, create_positive_map
 from ..layers.ground_transformer.decoder import SparseFeatureFusionTransformerDecoder, _Lin
@@ -40,16 +41,23 @@ class _Prompt:
         self.gt_instances_3d = types.SimpleNamespace()
 
 
+class _TextFeatMap:
+    """text_feat_map as a child of the bind bracket: the linear layer is made over the arena where it is bound"""
+
+    def bind(self, arena, prefix):
+        self.lin = _Lin(arena, prefix + 'weight', prefix + 'bias')
+
+    def __call__(self, x, need_dx=True):
+        return self.lin(x, need_dx=need_dx)
+
+
 @MODELS.register_module()
 class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
-    _version = 2
-
     def __init__(self, backbone, backbone_3d, bbox_head, neck=None, neck_3d=None, decoder=None, voxel_size=0.01,
                  num_queries=512, max_num_entities=256, coord_type='CAMERA', train_cfg=None, test_cfg=None,
                  data_preprocessor=None, use_xyz_feat=False, init_cfg=None, seed=0, device='cuda:0', text_encoder_cfg=None,
                  tokenizer=None, text_encoder_impl=None):
         assert neck is None and neck_3d is not None and decoder is not None
-        self.device = torch.device(device)
         self.backbone = MODELS.build(backbone)
         self.backbone.act16 = True              # feature maps only feed the projection fusion: bf16 activation storage
         self.backbone_3d = MODELS.build(backbone_3d)
@@ -59,7 +67,6 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         self.bbox_head = MODELS.build(bbox_head)
         self.decoder = SparseFeatureFusionTransformerDecoder(**decoder)
         self.embed_dims = self.decoder.embed_dims
-        self.data_preprocessor = MODELS.build(data_preprocessor, device=self.device) if data_preprocessor else None
         self.coord_type, self.train_cfg, self.test_cfg = coord_type, train_cfg, test_cfg
         self.num_queries = num_queries
         self.max_num_entities = self.bbox_head.contrastive_cfg.get('max_text_len', max_num_entities)
@@ -75,11 +82,9 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         if self.text_encoder_impl == 'hip':
             self.text_encoder = HipTextEncoder.from_module(self.text_encoder)
         self.text_dim = self.text_encoder.config.hidden_size
-        self.arena = ParamArena(grounder_specs(text_dim=self.text_dim, E=self.embed_dims, num_layers=self.decoder.num_layers,
-                                               ffn=self.decoder.ffn_channels, in_channels=self.neck_3d.in_channels), seed=seed)
-        self.training = True
-        self._bound = False
-        self._pf_init()
+        self.text_feat_map = _TextFeatMap()
+        self._init_base(grounder_specs(text_dim=self.text_dim, E=self.embed_dims, num_layers=self.decoder.num_layers,
+                                       ffn=self.decoder.ffn_channels, in_channels=self.neck_3d.in_channels), device, seed, data_preprocessor)
 
     # gradient buckets (data parallel): the backbones, the MinkNeck, and -- implicit last part -- decoder + head +
     # text_feat_map, whose gradients are complete first: four all-reduces, each under the backward of what precedes it
@@ -91,29 +96,20 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         self.text_encoder.to(self.device)
         return self
 
+    def _children(self):
+        return [(self.backbone, 'backbone.'), (self.backbone_3d, 'backbone_3d.'), (self.neck_3d, 'neck_3d.'),
+                (self.decoder, 'decoder.'), (self.bbox_head, 'bbox_head.'), (self.text_feat_map, 'text_feat_map.')]
+
     def _bind(self):
-        if not self._bound:
-            if self.arena.data.device != self.device:
-                self.arena.to(self.device)
-            if next(self.text_encoder.parameters()).device != self.device:
-                self.text_encoder.to(self.device)
-            E.begin_bind(id(self))
-            try:
-                self.backbone.bind(self.arena, 'backbone.')
-                self.backbone_3d.bind(self.arena, 'backbone_3d.')
-                self.neck_3d.bind(self.arena, 'neck_3d.')
-                self.decoder.bind(self.arena, 'decoder.')
-                self.bbox_head.bind(self.arena, 'bbox_head.')
-                self.text_feat_map = _Lin(self.arena, 'text_feat_map.weight', 'text_feat_map.bias')
-            finally:
-                E.end_bind()
-            self._bound = True
+        if not self._bound and next(self.text_encoder.parameters()).device != self.device:
+            self.text_encoder.to(self.device)
+        super()._bind()
 
     # The frozen RoBERTa is a submodule of the reference detector, so its weights are part of the reference's state dict
     # (`text_encoder.*`, sparse_featfusion_grounder.py:104-116): a checkpoint written here must carry them and a reference
     # grounding checkpoint must load them -- otherwise the prompts would be encoded by random weights (round-2 advisor).
     def state_dict(self):
-        sd = self.arena.state_dict()
+        sd = super().state_dict()
         for k, v in self.text_encoder.state_dict().items():
             sd['text_encoder.' + k] = v
         return sd
@@ -139,12 +135,6 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         if strict and (missing or unexpected):
             raise RuntimeError(f'load_state_dict: missing {missing[:5]}... unexpected {unexpected[:5]}...')
         return missing, unexpected
-
-    def train(self, mode=True):
-        self.training = mode
-        for m in (self.backbone_3d, self.neck_3d, self.decoder, self.bbox_head):
-            m.training = mode
-        return self
 
     # ------------------------------------------------------------------ text
     def start_text(self, batch_data_samples):
@@ -234,7 +224,7 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         out = self.neck_3d(x, len(batch_data_samples))
         # everything recorded from here on (text map, decoder, head) belongs to the last gradient part (3); once the reverse
         # replay is back here only fusion + neck closures remain before the 3-D backbone's: part 2 (neck_3d.) is theirs
-        self._tape_marks = self._tape_marks[:2] + [(len(E.TAPE.fns), 3)]
+        self.tape_part(3)
         return out
 
     def forward_transformer(self, text, tlen, T, batch_data_samples):
@@ -259,12 +249,8 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         query = E.gather_rows(feats, gidx)
         qcoords = torch.empty((B * Q, 3), dtype=torch.float32, device=dev)
         call('es_row_move', P(qcoords), 3, P(coords), 3, P(gidx), B * Q, 3, 0, s)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False                   # proposals: reg_branches[num_layers] on the selected tokens, detached
-        try:
+        with E.no_tape():                        # proposals: reg_branches[num_layers] on the selected tokens, detached
             pred0 = self.bbox_head.decode(qcoords, self.bbox_head.reg_branch(E.Var(query.d, rg=False))).d
-        finally:
-            E.TAPE.enabled = prev
         self.last_queries = dict(idx=idx, gidx=gidx, rowmax=rowmax, pred0=pred0, Q=Q, klen=klen)
         return self.decoder(query, feats, coords, qcoords, pred0, text, B, Q, Lmax, T, klen, tlen, self.bbox_head)
 
@@ -283,42 +269,25 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         return out
 
     def predict(self, batch_inputs_dict, batch_data_samples, **kwargs):
-        was = self.training
-        self.train(False)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False
-        try:
+        with self._predict_guard():
             self._bind()
             job = self.start_text(batch_data_samples)
             self.extract_feat(batch_inputs_dict, batch_data_samples)
             text, mask, tlen, T = self.finish_text(job, batch_data_samples)
             hidden, boxes = self.forward_transformer(text, tlen, T, batch_data_samples)
             results = self.bbox_head.predict(hidden, boxes, text, mask, batch_data_samples, tlen=tlen)
-        finally:
-            E.TAPE.enabled = prev
-            self.train(was)
         for ds, r in zip(batch_data_samples, results):
             ds.pred_instances_3d = r
         return batch_data_samples
 
     # ------------------------------------------------------------------ one scene, many prompts
+    @contextlib.contextmanager
     def _eval_guard(self):
-        """the eval / tape-off state of predict() as a context manager"""
-        import contextlib
-
-        @contextlib.contextmanager
-        def guard():
-            was, prev = self.training, E.TAPE.enabled
+        """the predict guard for the entry points that do not come through forward(): + launches on the current stream, bound"""
+        with self._predict_guard():
             hip.refresh_stream()
-            self.train(False)
-            E.TAPE.enabled = False
-            try:
-                self._bind()
-                yield
-            finally:
-                E.TAPE.enabled = prev
-                self.train(was)
-        return guard()
+            self._bind()
+            yield
 
     def scene_from_tokens(self, feats, points):
         """SceneEncoding of an (L, E) / (L, 3) pair of device tensors (MinkNeck tokens of one scan, e.g. from a cache file)"""
@@ -440,12 +409,8 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
         query = E.concat_rows([E.gather_rows_shared(feats, idx[sc * P_:(sc + 1) * P_], P_, Q, r0=sc * Lmax, L=lens[sc]) for sc in range(S)])
         qcoords = torch.empty((S * P_ * Q, 3), dtype=torch.float32, device=dev)
         call('es_row_move', P(qcoords), 3, P(coords), 3, P(gidx), S * P_ * Q, 3, 0, s)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False                   # proposals: reg_branches[num_layers] on the selected tokens, detached
-        try:
+        with E.no_tape():                        # proposals: reg_branches[num_layers] on the selected tokens, detached
             pred0 = self.bbox_head.decode(qcoords, self.bbox_head.reg_branch(E.Var(query.d, rg=False))).d
-        finally:
-            E.TAPE.enabled = prev
         self.last_queries = dict(idx=idx, gidx=gidx, rowmax=rowmaxes, pred0=pred0, Q=Q, klen=klen)
         return self.decoder.forward_shared_train(query, feats, coords, list(lens), Lmax, qcoords, pred0, text, S, P_, Q, T, tlen,
                                                  self.bbox_head)

@@ -10,12 +10,12 @@ from ... import hip
 from ... import engine as E
 from ... import sparse
 from ...hip import P, call
-from ...parallel import BucketedGradReducer, is_dist
-from ...params import ParamArena, detector_specs
+from ...params import detector_specs
 from ...registry import MODELS
 from ...sparse import SparseTensor
 from ..layers.fusion_layers.point_fusion import (batch_point_sample_level, batch_point_sample_level_bwd,
                                                  build_fusion_meta)
+from .base import DetectorBase
 
 
 def _stream():
@@ -23,77 +23,28 @@ def _stream():
 
 
 @MODELS.register_module()
-class SparseFeatureFusionSingleStage3DDetector:
-    _version = 2
-
+class SparseFeatureFusionSingleStage3DDetector(DetectorBase):
     def __init__(self, backbone, backbone_3d, bbox_head, neck=None, neck_3d=None, coord_type='CAMERA',
                  train_cfg=None, test_cfg=None, data_preprocessor=None, use_xyz_feat=False, init_cfg=None, seed=0,
                  device='cuda:0'):
         assert neck is None and neck_3d is None, 'the shipped mv-3ddet config has no necks'
-        self.device = torch.device(device)
         self.backbone = MODELS.build(backbone)
         self.backbone.act16 = True              # its feature maps only feed the projection fusion: bf16 activation storage
         self.backbone_3d = MODELS.build(backbone_3d)
         bbox_head = dict(bbox_head)
         bbox_head.update(train_cfg=train_cfg, test_cfg=test_cfg)
         self.bbox_head = MODELS.build(bbox_head)
-        self.data_preprocessor = MODELS.build(data_preprocessor, device=self.device) if data_preprocessor else None
         self.voxel_size = self.bbox_head.voxel_size
         self.use_xyz_feat = use_xyz_feat
         self.coord_type = coord_type
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        self.arena = ParamArena(detector_specs(self.bbox_head.num_classes), seed=seed)
-        self.training = True
-        self._bound = False
-        self._pf_init()
+        self._init_base(detector_specs(self.bbox_head.num_classes), device, seed, data_preprocessor)
         # The image branch (2-D backbone forward, and its backward) and the point branch (coordinate pipeline + 3-D
         # backbone) only meet in the fusion layer, so they are issued on two HIP streams (engine.side_stream): the deep,
         # under-filled sparse launches of the point branch then run in the shadow of the image branch's full-chip ones.
 
-    # ------------------------------------------------------------------ parameters
-    def to(self, device):
-        self.device = torch.device(device)
-        self.arena.to(self.device)
-        if self.data_preprocessor is not None:
-            self.data_preprocessor.to(self.device)
-        self._bound = False
-        return self
-
-    def _bind(self):
-        if not self._bound:
-            if self.arena.data.device != self.device:
-                self.arena.to(self.device)
-            E.begin_bind(id(self))               # conv kernels of an earlier bind of this detector are dropped
-            try:
-                self.backbone.bind(self.arena, 'backbone.')
-                self.backbone_3d.bind(self.arena, 'backbone_3d.')
-                self.bbox_head.bind(self.arena, 'bbox_head.')
-            finally:
-                E.end_bind()
-            self._bound = True
-
-    def __del__(self):
-        try:
-            E.release(id(self))
-        except Exception:
-            pass
-
-    def state_dict(self):
-        return self.arena.state_dict()
-
-    def load_state_dict(self, sd, strict=False, tap_order=None):
-        """reference-named state dict -> arena; returns (missing, unexpected) keys like torch.nn.Module does"""
-        res = self.arena.load_state_dict(sd, strict=strict, tap_order=tap_order)
-        E.WEIGHT_VERSION[0] += 1                 # bf16 weight copies are stale
-        if self._bound:
-            self.backbone.refresh()              # re-fold the frozen BatchNorm2d statistics
-        return res
-
-    def train(self, mode=True):
-        self.training = mode
-        self.backbone_3d.training = mode
-        self.bbox_head.training = mode
-        return self
+    def _children(self):
+        return [(self.backbone, 'backbone.'), (self.backbone_3d, 'backbone_3d.'), (self.bbox_head, 'bbox_head.')]
 
     # ------------------------------------------------------------------ next-batch prefetch (round 4)
     # The reference hides the data side of step i+1 behind step i with DataLoader workers (A1-A3 on host cores).  Here A1-A4 and
@@ -110,7 +61,8 @@ class SparseFeatureFusionSingleStage3DDetector:
     # next step.  They are kept referenced until the prefetch stream has waited for an event recorded on the main stream
     # at the end of the step that used them -- one step late, when that event has long fired -- so a recycled block can never
     # be rewritten by a prefetch kernel while a main-stream kernel still reads it.
-    def _pf_init(self):
+    def _init_base(self, specs, device, seed, data_preprocessor):
+        super()._init_base(specs, device, seed, data_preprocessor)
         self._pf_stream = None
         self._prefetched = None        # dict of the batch prepared ahead (consumed by the next train_step on the same `data`)
         self._pf_cur = None            # ... of the batch the running train_step is using
@@ -172,12 +124,13 @@ class SparseFeatureFusionSingleStage3DDetector:
                 break
 
     def _pf_take(self, data):
-        """train_step entry: the prefetched batch if `data` is the object prefetch() returned, else None"""
+        """train_step entry: the batch preprocessed, voxelised and mapped by prefetch() under the previous step if `data` is the
+        object prefetch() returned, else None"""
         pf, self._prefetched = self._prefetched, None
         if pf is not None and pf['data'] is data:
             hip.stream_obj().wait_event(pf['ready'])
             self._pf_cur = pf
-            return pf
+            return pf['pre']
         self._pf_cur = None
         return None
 
@@ -225,7 +178,8 @@ class SparseFeatureFusionSingleStage3DDetector:
             E.refresh_weight_copies()
             img_feats = self.backbone(nhwc)
         E.mark('A7 2-D backbone fwd')
-        self._tape_marks = [len(E.TAPE.fns)]                   # end of the 2-D backbone's closures
+        self.start_tape_parts()
+        self._branch_ends = [len(E.TAPE.fns), None]            # end of the 2-D backbone's closures, of the 3-D backbone's
         return img_feats, V, (H, W), forked
 
     def _fuse_points(self, batch_inputs_dict, batch_data_samples, image_branch):
@@ -259,7 +213,8 @@ class SparseFeatureFusionSingleStage3DDetector:
         if self._pf_stream is not None:                        # next-batch prefetch in use: its kernels start behind this point
             self._ev_3d_done = torch.cuda.Event()
             self._ev_3d_done.record(hip.stream_obj())
-        self._tape_marks.append(len(E.TAPE.fns))               # end of the 3-D backbone's closures
+        self._branch_ends[1] = len(E.TAPE.fns)
+        self.tape_part(2)                                      # behind them: fusion + head (a subclass records more parts)
         if forked:
             E.join_side()                        # image features are needed from here on
         outs = []
@@ -294,87 +249,23 @@ class SparseFeatureFusionSingleStage3DDetector:
     def predict(self, batch_inputs_dict, batch_data_samples, **kwargs):
         """sparse_featfusion_single_stage.py:245-280: detections are attached to the data samples as
         `pred_instances_3d` (and returned)."""
-        was = self.training
-        self.train(False)
-        prev = E.TAPE.enabled
-        E.TAPE.enabled = False
-        try:
+        with self._predict_guard():
             x = self.extract_feat(batch_inputs_dict, batch_data_samples)
             results = self.bbox_head.predict(x, batch_data_samples, **kwargs)
-        finally:
-            E.TAPE.enabled = prev
-            self.train(was)
         for ds, r in zip(batch_data_samples, results):
             ds.pred_instances_3d = r
         return batch_data_samples
 
-    def forward(self, inputs, data_samples=None, mode='tensor', **kwargs):
-        hip.refresh_stream()                     # launches follow torch's CURRENT stream of this call
-        if mode == 'loss':
-            return self.loss(inputs, data_samples, **kwargs)
-        elif mode == 'predict':
-            return self.predict(inputs, data_samples, **kwargs)
-        raise RuntimeError(f'Invalid mode "{mode}". Only supports loss, predict and tensor mode')
+    _stages = ('A1-A3 depth->points', 'A10-A16 head fwd + targets + losses', 'backward (head, 3-D, 2-D)',
+               'all-reduce wait + clip + AdamW')
 
-    __call__ = forward
+    # gradient buckets of the data-parallel exchange: the base's -- parts 0 / 1 = the backbones, the implicit last part (2) =
+    # everything else (head); subclasses add groups and tape_part() calls for what sits behind the fusion
 
-    def train_step(self, data, optim_wrapper):
-        """mmengine BaseModel.train_step: preprocess, loss forward, sum of the 'loss' entries, backward, update."""
-        return self._train_step(data, optim_wrapper, lambda inputs, samples: self.forward(inputs, samples, mode='loss'))
-
-    def _train_step(self, data, optim_wrapper, loss_fn):
-        """the body of train_step with the loss forward as a callable (inputs, data_samples) -> loss dict (the grounder's
-        train_step_shared passes loss_shared)"""
-        E.settle_gc(self)                        # (the collector's generations are frozen once the warm-up steps are through)
-        E.TAPE.clear()
-        hip.refresh_stream()
-        E.mark('A1-A3 depth->points')            # whatever the caller queued before train_step (pipeline.make_batch)
-        pf = self._pf_take(data)
-        if pf is not None:
-            data = pf['pre']                     # preprocessed, voxelised and mapped by prefetch() under the previous step
-        elif self.data_preprocessor is not None:
-            data = self.data_preprocessor(data, True)
-        self._bind()
-        self.arena.grad.zero_()
-        E.new_grad_epoch()                       # first weight-gradient launch per weight overwrites, later ones add
-        losses = loss_fn(data['inputs'], data['data_samples'])
-        E.mark('A10-A16 head fwd + targets + losses')
-        if is_dist():
-            # bucketed gradient all-reduce overlapped with backward: markers fire when the tape (run in reverse) has
-            # finished the head (+ fusion) closures, then the 3-D backbone's, then everything
-            if getattr(self.arena, 'reducer', None) is None:
-                self.arena.reducer = BucketedGradReducer(self.arena, groups=self._bucket_groups)
-            red = self.arena.reducer
-            self._backward(red)
-        else:
-            self._backward(None)
-        E.mark('backward (head, 3-D, 2-D)')
-        optim_wrapper.update_params(self.arena)
-        E.mark('all-reduce wait + clip + AdamW')
-        self._pf_done()
-        return losses
-
-    # gradient buckets of the data-parallel exchange (parallel.BucketedGradReducer): parts 0 / 1 = the backbones, the
-    # implicit last part = everything else (head); subclasses add parts and tape marks for what sits behind the fusion
-    _bucket_groups = (('backbone.',), ('backbone_3d.',))
-
-    def _backward(self, red):
-        """Run the tape in reverse: head + fusion, then the 3-D backbone on the main stream while the 2-D backbone's
-        backward runs on the side stream (they share nothing but the fusion gradients).  `red` (data parallel only)
-        all-reduces each part of the gradient arena as soon as it is complete.  `_tape_marks` = [end of the 2-D
-        backbone's closures, end of the 3-D backbone's, *(tape index, part) pairs a subclass recorded behind them*]: when
-        the reverse replay has passed a pair's index, that part's gradients are complete."""
-        fns = E.TAPE.fns
-        m2d, m3d = self._tape_marks[:2]
-        extra = sorted(self._tape_marks[2:], reverse=True) + [(m3d, 2)]     # part 2: what sits between the 3-D backbone and the marks
-        hi = len(fns)
-        for idx, part in extra:                                # (the last pair: everything behind the backbones)
-            for fn in reversed(fns[idx:hi]):
-                fn()
-            hi = idx
-            if red is not None:
-                E.join_wgrad_streams(final=False)
-                red.launch(part)                               # e.g. head gradients complete
+    def _backward_head(self, fns, red, done):
+        """The two backbones' closures (head + fusion ran before, part by part): the 3-D backbone on the main stream while the 2-D
+        backbone's backward runs on the side stream (they share nothing but the fusion gradients)."""
+        m2d, m3d = self._branch_ends
         img, pts = fns[:m2d][::-1], fns[m2d:m3d][::-1]
         if E.TWO_STREAMS[0] and img and pts:
             # issue the two branches in alternating chunks so that neither queue runs dry while the host is busy
@@ -400,4 +291,3 @@ class SparseFeatureFusionSingleStage3DDetector:
         E.join_wgrad_streams()
         if red is not None:
             red.launch(0)                                      # 2-D backbone gradients complete
-        E.TAPE.clear()

@@ -1,0 +1,232 @@
+"""The protocol the five detectors share through models/detectors/base.py (no GPU).
+
+Replay order: `_backward` is run on bare instances over a tape of logging closures with engine.side_stream / join_side /
+join_wgrad_streams replaced by loggers and a stub reducer.  The expected logs in REPLAY were NOT derived by hand and not taken
+from the code under test: this same script (with `_arm` writing the field names of that time) was run on the commit before
+the sparse-fusion family moved onto DetectorBase, and the lists it printed are pasted below.  Log entries: 'f<i>' closure i of
+the tape, 's+1' / 's+0' side stream entered with fork / without, 's-' side stream left, 'js' join_side, 'w1' / 'w0'
+join_wgrad_streams(final=True / False), 'L<p>' reducer.launch(p).
+
+Mode switching, bind order, the predict guard and the state-dict keys: every detector is built on the CPU from the project's
+configs; the key lists in tests/golden/detector_state_keys.json were written at the same earlier commit."""
+import json
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KEYS = os.path.join(ROOT, 'tests', 'golden', 'detector_state_keys.json')
+
+# layout -> (closures of the 2-D branch, of the 3-D branch, of the rest, [(tape index, part)], parts of the reducer)
+LAYOUTS = {'single': (7, 5, 4, [(12, 2)], 3),
+           'grounder': (7, 5, 4, [(12, 2), (14, 3)], 4),
+           'empty2d': (0, 5, 4, [(5, 2)], 3),
+           'occ': (0, 0, 12, [(3, 1), (6, 2), (9, 3)], 4)}
+CASES = [('SparseFeatureFusionSingleStage3DDetector', 'single'), ('SparseFeatureFusionSingleStage3DDetector', 'empty2d'),
+         ('Embodied3DDetector', 'single'), ('Embodied3DDetector', 'empty2d'),
+         ('SparseFeatureFusion3DGrounder', 'grounder'), ('SparseFeatureFusion3DGrounder', 'empty2d'),
+         ('DenseFusionOccPredictor', 'occ'), ('EmbodiedOccPredictor', 'occ')]
+
+# (layout, reducer given, TWO_STREAMS) -> log, recorded at the parent commit (see the module docstring)
+REPLAY = {
+    ('single', True, True): [
+        'f15', 'f14', 'f13', 'f12', 'w0', 'L2', 's+1', 'f6', 's-', 's+0', 'f5', 's-', 'f11', 's+0', 'f4', 's-', 'f10',
+        's+0', 'f3', 's-', 'f9', 's+0', 'f2', 's-', 'f8', 's+0', 'f1', 'f0', 's-', 'f7', 'w0', 'L1', 'js', 'w1', 'L0'],
+    ('single', True, False): [
+        'f15', 'f14', 'f13', 'f12', 'w0', 'L2', 'f11', 'f10', 'f9', 'f8', 'f7', 'w0', 'L1', 'f6', 'f5', 'f4', 'f3',
+        'f2', 'f1', 'f0', 'w1', 'L0'],
+    ('single', False, True): [
+        'f15', 'f14', 'f13', 'f12', 's+1', 'f6', 's-', 's+0', 'f5', 's-', 'f11', 's+0', 'f4', 's-', 'f10', 's+0', 'f3',
+        's-', 'f9', 's+0', 'f2', 's-', 'f8', 's+0', 'f1', 'f0', 's-', 'f7', 'js', 'w1'],
+    ('single', False, False): [
+        'f15', 'f14', 'f13', 'f12', 'f11', 'f10', 'f9', 'f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+    ('empty2d', True, True): ['f8', 'f7', 'f6', 'f5', 'w0', 'L2', 'f4', 'f3', 'f2', 'f1', 'f0', 'w0', 'L1', 'w1', 'L0'],
+    ('empty2d', True, False): ['f8', 'f7', 'f6', 'f5', 'w0', 'L2', 'f4', 'f3', 'f2', 'f1', 'f0', 'w0', 'L1', 'w1', 'L0'],
+    ('empty2d', False, True): ['f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+    ('empty2d', False, False): ['f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+    ('grounder', True, True): [
+        'f15', 'f14', 'w0', 'L3', 'f13', 'f12', 'w0', 'L2', 's+1', 'f6', 's-', 's+0', 'f5', 's-', 'f11', 's+0', 'f4',
+        's-', 'f10', 's+0', 'f3', 's-', 'f9', 's+0', 'f2', 's-', 'f8', 's+0', 'f1', 'f0', 's-', 'f7', 'w0', 'L1', 'js',
+        'w1', 'L0'],
+    ('grounder', True, False): [
+        'f15', 'f14', 'w0', 'L3', 'f13', 'f12', 'w0', 'L2', 'f11', 'f10', 'f9', 'f8', 'f7', 'w0', 'L1', 'f6', 'f5',
+        'f4', 'f3', 'f2', 'f1', 'f0', 'w1', 'L0'],
+    ('grounder', False, True): [
+        'f15', 'f14', 'f13', 'f12', 's+1', 'f6', 's-', 's+0', 'f5', 's-', 'f11', 's+0', 'f4', 's-', 'f10', 's+0', 'f3',
+        's-', 'f9', 's+0', 'f2', 's-', 'f8', 's+0', 'f1', 'f0', 's-', 'f7', 'js', 'w1'],
+    ('grounder', False, False): [
+        'f15', 'f14', 'f13', 'f12', 'f11', 'f10', 'f9', 'f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+    ('occ', True, True): [
+        'f11', 'f10', 'f9', 'w0', 'L3', 'f8', 'f7', 'f6', 'w0', 'L2', 'f5', 'f4', 'f3', 'w0', 'L1', 'f2', 'f1', 'f0',
+        'w1', 'L0'],
+    ('occ', True, False): [
+        'f11', 'f10', 'f9', 'w0', 'L3', 'f8', 'f7', 'f6', 'w0', 'L2', 'f5', 'f4', 'f3', 'w0', 'L1', 'f2', 'f1', 'f0',
+        'w1', 'L0'],
+    ('occ', False, True): ['f11', 'f10', 'f9', 'f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+    ('occ', False, False): ['f11', 'f10', 'f9', 'f8', 'f7', 'f6', 'f5', 'f4', 'f3', 'f2', 'f1', 'f0', 'w1'],
+}
+
+
+def _arm(det, layout):
+    """the fields _backward reads"""
+    n2, n3, _, parts, _ = LAYOUTS[layout]
+    det._tape_parts = list(parts)
+    det._branch_ends = (n2, n2 + n3)
+
+
+def _cls(name):
+    from embodiedscan_amd import models  # noqa: F401  (registers the classes)
+    from embodiedscan_amd.registry import MODELS
+    return MODELS.get(name)
+
+
+def run_backward(monkeypatch, name, layout, with_red, two, arm=None):
+    from embodiedscan_amd import engine as E
+    log = []
+
+    class side:
+        def __init__(self, fork=True):
+            self.fork = fork
+
+        def __enter__(self):
+            log.append(f's+{int(bool(self.fork))}')
+
+        def __exit__(self, *exc):
+            log.append('s-')
+
+    class Red:
+        parts = [None] * LAYOUTS[layout][4]
+
+        def launch(self, part):
+            log.append(f'L{part}')
+
+    monkeypatch.setattr(E, 'side_stream', side)
+    monkeypatch.setattr(E, 'join_side', lambda: log.append('js'))
+    monkeypatch.setattr(E, 'join_wgrad_streams', lambda final=True: log.append(f'w{int(bool(final))}'))
+    monkeypatch.setattr(E, 'TWO_STREAMS', [two])
+    det = object.__new__(_cls(name))
+    (arm or _arm)(det, layout)
+    n = sum(LAYOUTS[layout][:3])
+    E.TAPE.clear()
+    E.TAPE.fns = [(lambda i=i: log.append(f'f{i}')) for i in range(n)]
+    try:
+        det._backward(Red() if with_red else None)
+        assert E.TAPE.fns == []
+    finally:
+        E.TAPE.clear()
+    return log
+
+
+@pytest.mark.parametrize('two', [True, False])
+@pytest.mark.parametrize('with_red', [True, False])
+@pytest.mark.parametrize('name,layout', CASES)
+def test_backward_replay_order_is_the_parents(monkeypatch, name, layout, with_red, two):
+    log = run_backward(monkeypatch, name, layout, with_red, two)
+    print(log)
+    assert log == REPLAY[(layout, with_red, two)]
+
+
+# ----------------------------------------------------------------------------- built detectors (CPU, no kernel runs)
+CONFIGS = {'SparseFeatureFusionSingleStage3DDetector': 'mv_3ddet.py', 'SparseFeatureFusion3DGrounder': 'mv_grounding.py',
+           'Embodied3DDetector': 'cont_det3d.py', 'DenseFusionOccPredictor': 'mv_occ.py', 'EmbodiedOccPredictor': 'cont_occ.py'}
+SPARSE = ['backbone.', 'backbone_3d.', 'bbox_head.']
+OCC = ['backbone.', 'neck.', 'backbone_3d.', 'neck_3d.', 'bbox_head.']
+# class -> (prefixes of _children() in bind order, the modules whose `training` flag train() flipped at the parent commit)
+EXPECT = {'SparseFeatureFusionSingleStage3DDetector': (SPARSE, ['backbone_3d', 'bbox_head']),
+          'Embodied3DDetector': (SPARSE, ['backbone_3d', 'bbox_head']),
+          'SparseFeatureFusion3DGrounder': (['backbone.', 'backbone_3d.', 'neck_3d.', 'decoder.', 'bbox_head.', 'text_feat_map.'],
+                                            ['backbone_3d', 'bbox_head', 'decoder', 'neck_3d']),
+          'DenseFusionOccPredictor': (OCC, ['backbone_3d', 'bbox_head', 'neck_3d']),
+          'EmbodiedOccPredictor': (OCC, ['backbone_3d', 'bbox_head', 'neck_3d'])}
+
+
+@pytest.fixture(scope='module')
+def detectors():
+    from embodiedscan_amd.config import build_detector
+    return {name: build_detector(os.path.join(ROOT, 'configs', cfg), device='cpu') for name, cfg in CONFIGS.items()}
+
+
+def _flags(det):
+    return {k: v.training for k, v in vars(det).items() if hasattr(v, 'training')}
+
+
+@pytest.mark.parametrize('name', list(CONFIGS))
+def test_children_and_mode_switching(detectors, name):
+    from embodiedscan_amd.models.detectors.base import DetectorBase
+    det = detectors[name]
+    prefixes, flipped = EXPECT[name]
+    assert type(det).__name__ == name and isinstance(det, DetectorBase)
+    assert [p for _, p in det._children()] == prefixes
+    assert all(hasattr(m, 'bind') for m, _ in det._children())
+    assert [p for m, p in det._children() if hasattr(m, 'refresh')] == ['backbone.']     # what load_state_dict refreshes
+    before = _flags(det)
+    assert det.training is True and det.train(False) is det and det.training is False
+    off = _flags(det)
+    assert sorted(k for k in before if off[k] != before[k]) == flipped and not any(off[k] for k in flipped)
+    det.train(True)
+    assert det.training is True and _flags(det) == before and all(before[k] for k in flipped)
+
+
+@pytest.mark.parametrize('name', list(CONFIGS))
+def test_protocol_methods_are_the_bases(name):
+    """the sparse fusion family defines none of the shared protocol; the grounder's overrides are the text encoder's"""
+    from embodiedscan_amd.models.detectors.base import DetectorBase
+    allowed = {'to', 'state_dict', 'load_state_dict', '_bind'} if name == 'SparseFeatureFusion3DGrounder' else set()
+    for attr in ('to', '_bind', '__del__', 'state_dict', 'load_state_dict', 'train', 'forward', '__call__', 'train_step', '_train_step',
+                 '_backward', '_predict_guard', 'tape_part', 'start_tape_parts'):
+        if attr not in allowed:
+            assert getattr(_cls(name), attr) is getattr(DetectorBase, attr), attr
+    assert _cls(name).__call__ is DetectorBase.forward
+
+
+@pytest.mark.parametrize('name', list(CONFIGS))
+def test_predict_guard_restores_both_flags_when_the_body_raises(detectors, name):
+    from embodiedscan_amd import engine as E
+    det = detectors[name]
+    for training, tape in ((True, True), (False, True), (True, False)):
+        det.train(training)
+        E.TAPE.enabled = tape
+        try:
+            with pytest.raises(ZeroDivisionError):
+                with det._predict_guard():
+                    assert det.training is False and E.TAPE.enabled is False
+                    assert not any(_flags(det)[k] for k in EXPECT[name][1])
+                    1 / 0
+            assert det.training is training and E.TAPE.enabled is tape
+            assert all(_flags(det)[k] is training for k in EXPECT[name][1])
+        finally:
+            E.TAPE.enabled = True
+            det.train(True)
+
+
+def test_no_tape_restores_the_previous_value():
+    from embodiedscan_amd import engine as E
+    assert E.TAPE.enabled is True
+    with E.no_tape():
+        assert E.TAPE.enabled is False
+        with E.no_tape():                       # nested: the inner exit leaves the tape off
+            E.TAPE.add(lambda: None)
+        assert E.TAPE.enabled is False and E.TAPE.fns == []
+    assert E.TAPE.enabled is True
+    with pytest.raises(KeyError):
+        with E.no_tape():
+            raise KeyError
+    assert E.TAPE.enabled is True
+
+
+@pytest.mark.parametrize('name', list(CONFIGS))
+def test_state_dict_keys_are_the_parents(detectors, name):
+    with open(KEYS) as f:
+        want = json.load(f)[name]
+    assert list(detectors[name].state_dict().keys()) == want
+
+
+@pytest.mark.parametrize('name', list(CONFIGS))
+def test_loss_forward_resets_the_gradient_parts(monkeypatch, name):
+    """start_tape_parts() is what a loss forward calls first: parts recorded by an earlier forward never reach _backward"""
+    det = object.__new__(_cls(name))
+    _arm(det, 'occ')
+    det.start_tape_parts()
+    assert det._tape_parts == []
+    det.tape_part(1)
+    assert det._tape_parts == [(0, 1)]

@@ -47,7 +47,6 @@ def run():
         det._bind()
         det.arena.grad.zero_()
         E.new_grad_epoch()
-        det._tape_parts = []
         losses = det.forward(data['inputs'], data['data_samples'], mode='loss')
         torch.cuda.synchronize()
         rec = [('loss ' + k, bits(v.reshape(1) if torch.is_tensor(v) else torch.tensor([float(v)]))) for k, v in losses.items()]
