@@ -12,6 +12,7 @@ selects smaller n there; every V and C is kept)."""
 import pytest
 import torch
 
+import fusion_geom_spec as G
 import prefix_spec as S
 
 pytestmark = pytest.mark.gpu
@@ -85,6 +86,7 @@ def fwd_case(dev, stats, case, ldo_pad):
         assert _bits_equal(o_t, out[t * n:(t + 1) * n]), f'{label}: rows of prefix {t} are not bit-equal to the {t + 1}-view call'
     rec = dict(case, coords=coords, feats=feats, out=out, pix=pix, cnt=cnt, obuf=obuf, ldo=ldo)
     S.check_prefix_fwd(rec, dev, stats)                   # (b)
+    G.check_geometry(rec, dev, caps=False, label=label)   # pix and cnt themselves, against the f64 geometry
     return rec
 
 

@@ -12,6 +12,7 @@ smaller n there; every T and C is kept)."""
 import pytest
 import torch
 
+import fusion_geom_spec as G
 import prefix_spec as S
 import walk_spec as W
 from test_gpu_prefix_fusion import SENT, _band_ok, _banded, _bits_equal, _hip, _small, _st
@@ -74,6 +75,7 @@ def walk_case(dev, stats, case, ldo_pad):
     W.same_as_prefix(label, steps, prefix(dev, case))                                           # (a)
     dcase = dict(case, coords=case['coords'].to(dev), feats=case['feats'].to(dev))
     W.check_walk(dcase, steps, dev, stats)                                                     # (b)
+    G.check_geometry(W.assemble(dcase, steps), dev, caps=False, label=label)                   # pix and nvalid against the f64 geometry
     again, state2 = walk(dev, case, ldo_pad, label)                                            # (c)
     for t, (s, r) in enumerate(zip(steps, again)):
         assert _bits_equal(s['out'], r['out']) and torch.equal(s['nvalid'], r['nvalid']) and torch.equal(s['pix'], r['pix']), \

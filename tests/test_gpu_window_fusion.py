@@ -12,6 +12,7 @@ Every body is a function of `dev`: tests/test_emu_window_fusion.py runs the same
 import pytest
 import torch
 
+import fusion_geom_spec as G
 import window_spec as S
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +100,7 @@ def fwd_case(dev, stats, case, half, ldo_pad=0):
     assert _bits_equal(out, yard['out']), f'{label}: rows are not bit-equal to the yardstick'
     rec = dict(yard, out=out.contiguous(), pix=pix, cnt=cnt, win=win)
     S.check_win_fwd(rec, dev, stats)
+    G.check_geometry(rec, dev, vs=S.VS, caps=False, label=label)      # pix and cnt themselves, against the f64 geometry
     return rec, yard
 
 
