@@ -46,6 +46,16 @@ train_pipeline = [
     dict(type='GlobalRotScaleTrans', rot_range=[-0.087266, 0.087266], scale_ratio_range=[.9, 1.1],
          translation_std=[.1, .1, .1], shift_height=False),
     dict(type='Pack3DDetInputs', keys=['img', 'points', 'gt_bboxes_3d', 'gt_labels_3d'])]
+test_pipeline = [
+    dict(type='LoadAnnotations3D'),
+    dict(type='MultiViewPipeline', n_images=50, ordered=True,
+         transforms=[dict(type='LoadImageFromFile'), dict(type='LoadDepthFromFile'),
+                     dict(type='ConvertRGBDToPoints', coord_type='CAMERA'),
+                     dict(type='PointSample', num_points=n_points // 10),
+                     dict(type='Resize', scale=(480, 480), keep_ratio=False)]),
+    dict(type='AggregateMultiViewPoints', coord_type='DEPTH'),
+    dict(type='PointSample', num_points=n_points),
+    dict(type='Pack3DDetInputs', keys=['img', 'points', 'gt_bboxes_3d', 'gt_labels_3d'])]
 train_dataloader = dict(batch_size=12, num_workers=12, sampler=dict(type='DefaultSampler', shuffle=True),
                         dataset=dict(type='RepeatDataset', times=1,
                                      dataset=dict(type='MultiView3DGroundingDataset', data_root='data',

@@ -237,6 +237,219 @@ extern "C" int es_box3d_iou_filter(const float* boxes, const float* scores, cons
   return 0;
 }
 
+// ------------------------------------------------------------------ box_iou3d with its two polygons in LDS
+// faces_flux keeps two 16-vertex polygons per lane in scratch (1 KB).  The same routine with the polygons in an LDS column per lane
+// -- vertex i, component c of lane q at [(i * 3 + c) * CLIP_LANES + q], so that a wave's accesses are conflict free -- and the two
+// face loops unrolled, so that every box axis is indexed statically and nothing is left for scratch.  The SAME expressions in the
+// same order on the same values (no FMA contraction in this file): bit for bit the value box_iou3d returns.  The clipped polygon is
+// written to the other column set and the two swap, where faces_flux copies it back: the values read are the same.
+#define CLIP_LANES 64
+__device__ inline V3 lp_get(const double* p, int i) {
+  return v3(p[(i * 3 + 0) * CLIP_LANES], p[(i * 3 + 1) * CLIP_LANES], p[(i * 3 + 2) * CLIP_LANES]);
+}
+__device__ inline void lp_set(double* p, int i, V3 v) {
+  p[(i * 3 + 0) * CLIP_LANES] = v.x; p[(i * 3 + 1) * CLIP_LANES] = v.y; p[(i * 3 + 2) * CLIP_LANES] = v.z;
+}
+__device__ inline double faces_flux_lds(const OBox& P, const OBox& Q, V3 O, bool inclusive, double* poly, double* tmp) {
+  double total = 0.0;
+#pragma unroll
+  for (int f = 0; f < 6; ++f) {
+    const int j = f >> 1, k = (j + 1) % 3, l = (j + 2) % 3;
+    const double sgn = (f & 1) ? -1.0 : 1.0;
+    V3 n = P.ax[j] * sgn;
+    V3 fc = P.c + P.ax[j] * (sgn * P.h[j]);
+    V3 ek = P.ax[k] * P.h[k], el = P.ax[l] * P.h[l];
+    int np = 4;
+    lp_set(poly, 0, fc + ek + el); lp_set(poly, 1, fc - ek + el); lp_set(poly, 2, fc - ek - el); lp_set(poly, 3, fc + ek - el);
+#pragma unroll
+    for (int g = 0; g < 6; ++g) {
+      if (np > 0) {
+        const int jj = g >> 1;
+        const double sg = (g & 1) ? -1.0 : 1.0;
+        V3 m = Q.ax[jj] * sg;
+        const double off = Q.h[jj];
+        int nt = 0;
+        for (int i = 0; i < np; ++i) {
+          V3 a = lp_get(poly, i), b = lp_get(poly, (i + 1) % np);
+          double da = dot3(m, a - Q.c) - off, db = dot3(m, b - Q.c) - off;
+          const bool same = inclusive && dot3(m, n) > 0.5;
+          bool ia = (da < -1e-12) || (same && da <= 1e-12), ib = (db < -1e-12) || (same && db <= 1e-12);
+          if (ia) { if (nt < MAXV) lp_set(tmp, nt++, a); }
+          if (ia != ib) {
+            double t = da / (da - db);
+            if (nt < MAXV) lp_set(tmp, nt++, a + (b - a) * t);
+          }
+        }
+        np = nt;
+        double* sw = poly; poly = tmp; tmp = sw;
+      }
+    }
+    if (np < 3) continue;
+    V3 av = v3(0, 0, 0);
+    const V3 p0 = lp_get(poly, 0);
+    for (int i = 1; i + 1 < np; ++i) av = av + cross3(lp_get(poly, i) - p0, lp_get(poly, i + 1) - p0);
+    double area = 0.5 * sqrt(dot3(av, av));
+    total += dot3(n, fc - O) * area;
+  }
+  return total;
+}
+// make_box on the six values make_box computes first (t = cos, sin of b[6], b[7], b[8]): the same three axis expressions
+__device__ inline OBox make_box_trig(const double* b, const double* t, int ld) {
+  OBox o;
+  o.c = v3(b[0], b[1], b[2]);
+  o.h[0] = b[3] * 0.5; o.h[1] = b[4] * 0.5; o.h[2] = b[5] * 0.5;
+  double ca = t[0], sa = t[ld], cb = t[2 * ld], sb = t[3 * ld], cc = t[4 * ld], sc = t[5 * ld];
+  o.ax[0] = v3(ca * cc - sa * sb * sc, sa * cc + ca * sb * sc, -(cb * sc));
+  o.ax[1] = v3(-(sa * cb), ca * cb, sb);
+  o.ax[2] = v3(ca * sc + sa * sb * cc, sa * sc - ca * sb * cc, cb * cc);
+  return o;
+}
+__device__ inline double box_iou3d_lds(const double* a9, const OBox& A, const double* b9, const OBox& B, double* poly, double* tmp) {
+  double va = a9[3] * a9[4] * a9[5], vb = b9[3] * b9[4] * b9[5];
+  V3 d = A.c - B.c;
+  double ra = sqrt(A.h[0] * A.h[0] + A.h[1] * A.h[1] + A.h[2] * A.h[2]), rb = sqrt(B.h[0] * B.h[0] + B.h[1] * B.h[1] + B.h[2] * B.h[2]);
+  if (dot3(d, d) > (ra + rb) * (ra + rb)) return 0.0;
+  double v = (faces_flux_lds(A, B, A.c, true, poly, tmp) + faces_flux_lds(B, A, A.c, false, poly, tmp)) / 3.0;
+  if (v < 0.0) v = 0.0;
+  return v / (va + vb - v);
+}
+
+// ------------------------------------------------------------------ answers of a grounder: distinct boxes per prompt, all prompts in one launch
+// ground() returns Q boxes and scores per prompt; an answer is the short list the greedy above leaves of them with ONE class:
+// rows by descending score (ties to the lower row), a row below score_thr or with a NaN score is never an answer, a row whose
+// 9-DoF IoU with an already kept row exceeds iou_thr is skipped (candidate first, f64 rounded to f32, f32 compare, a NaN IoU does
+// not suppress), and the walk stops at topk kept rows.  One workgroup per prompt; the order is made here: position of row i = the
+// number of rows j with s_j > s_i, or s_j == s_i and j < i (counted over the keys in LDS; a NaN score takes the key -inf, which
+// keeps the positions a permutation).  Then the two-phase pass of k_box3d_iou_filter without class counters.  The pass behind the
+// last kept row is not run (topk = 1 computes no IoU).  ans_idx[k] = -1 for k >= ans_cnt: every entry of the prompt's row is written.
+// Phase 2 clips with box_iou3d_lds on the first wave, one list entry per lane and 64 per round: the kernel uses no scratch and
+// spills nothing.  What makes that possible is the table s_trig (dynamic LDS, 48 Q bytes): the six sin / cos of every row, made
+// once in a loop of its own before the greedy -- the f64 sin / cos keep some fifty scalar registers of constants alive around
+// them, and inside the greedy loop those would stay live through the clipping (10 scalar spills measured with make_box there).
+#define GANS_MAX 1024              // rows per prompt: positions and keys of one prompt stay in LDS (9 KB)
+__global__ __launch_bounds__(FILT_T) void k_ground_answers(const float* __restrict__ boxes, const float* __restrict__ scores, int Q,
+                                                           float iou_thr, float score_thr, int topk, int* __restrict__ ans_idx,
+                                                           int* __restrict__ ans_cnt) {
+  __shared__ float s_key[GANS_MAX];
+  __shared__ unsigned short s_ord[GANS_MAX];       // row at each sorted position
+  __shared__ unsigned char s_dead[GANS_MAX];       // per sorted position
+  __shared__ unsigned short s_list[GANS_MAX];      // positions whose sphere meets the kept row's
+  __shared__ int s_first[FILT_T / 64];
+  __shared__ int s_m, s_nlist;
+  __shared__ double s_poly[2][MAXV * 3 * CLIP_LANES];      // the clipping's two polygons, one column per lane of the first wave (48 KB)
+  extern __shared__ double s_trig[];       // (6, Q): cos, sin of every row's three angles -- made once, in a loop of its own: the f64
+                                           // sin / cos hold ~50 scalar registers of constants, which must not stay live through the clipping
+  __shared__ float s_kb[9];                // the kept row's box: read back per lane, so that what is derived from it stays in vector registers
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  boxes += (size_t)blockIdx.x * Q * 9;
+  scores += (size_t)blockIdx.x * Q;
+  int* __restrict__ out = ans_idx + (size_t)blockIdx.x * topk;
+  for (int i = tid; i < Q; i += FILT_T) {
+    const float v = scores[i];
+    s_key[i] = (v != v) ? -__builtin_huge_valf() : v;
+  }
+  if (tid == 0) s_m = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = tid; i < Q; i += FILT_T) {
+    const float v = s_key[i];
+    int r = 0;
+    for (int j = 0; j < Q; ++j) {          // (every lane reads the same key: an LDS broadcast)
+      const float u = s_key[j];
+      r += (u > v || (u == v && j < i)) ? 1 : 0;
+    }
+    const float raw = scores[i];
+    const bool live = raw == raw && !(raw < score_thr);
+    s_ord[r] = (unsigned short)i;
+    s_dead[r] = live ? 0 : 1;
+    if (live) mine = max(mine, r + 1);
+  }
+  if (mine) atomicMax(&s_m, mine);
+  if (topk > 1) {                          // (topk = 1 computes no IoU)
+    for (int i = tid; i < Q; i += FILT_T) {
+      const double ea = boxes[(size_t)i * 9 + 6], eb = boxes[(size_t)i * 9 + 7], ec = boxes[(size_t)i * 9 + 8];
+      s_trig[i] = cos(ea); s_trig[Q + i] = sin(ea); s_trig[2 * Q + i] = cos(eb); s_trig[3 * Q + i] = sin(eb);
+      s_trig[4 * Q + i] = cos(ec); s_trig[5 * Q + i] = sin(ec);
+    }
+  }
+  __syncthreads();
+  const int m = s_m;                       // one past the last live position
+  int nk = 0, cur = 0;
+  while (nk < topk) {
+    // the first live position at or after `cur` (the same value in every lane)
+    int found = -1;
+    for (int base = cur; base < m; base += FILT_T) {
+      const int p = base + tid;
+      const bool ok = p < m && !s_dead[p];
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0) s_first[w] = bal ? base + w * 64 + __ffsll(bal) - 1 : 0x7fffffff;
+      __syncthreads();
+      int f = s_first[0];
+#pragma unroll
+      for (int k = 1; k < FILT_T / 64; ++k) f = min(f, s_first[k]);
+      __syncthreads();                     // every lane has read s_first before the next chunk rewrites it
+      if (f != 0x7fffffff) { found = f; break; }
+    }
+    if (found < 0) break;
+    const int rk = s_ord[found];
+    if (tid == 0) { out[nk] = rk; s_nlist = 0; }
+    ++nk;
+    if (nk == topk) break;                 // nothing is selected behind the last answer: its pass is not run
+    if (tid < 9) s_kb[tid] = boxes[(size_t)rk * 9 + tid];
+    __syncthreads();
+    double kb[9], a[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) kb[c] = s_kb[c];
+    const V3 kc = v3(kb[0], kb[1], kb[2]);
+    const double kr = filt_radius(kb);
+    for (int p = found + 1 + tid; p < m; p += FILT_T) {
+      if (s_dead[p]) continue;
+      const int r = s_ord[p];
+      const V3 d = v3((double)boxes[(size_t)r * 9], (double)boxes[(size_t)r * 9 + 1], (double)boxes[(size_t)r * 9 + 2]) - kc;
+      a[3] = boxes[(size_t)r * 9 + 3]; a[4] = boxes[(size_t)r * 9 + 4]; a[5] = boxes[(size_t)r * 9 + 5];
+      const double rs = filt_radius(a) + kr;
+      if (dot3(d, d) > rs * rs) {          // box_iou3d returns 0.0 here
+        if (0.0f > iou_thr) s_dead[p] = 1;
+      } else {
+        s_list[atomicAdd(&s_nlist, 1)] = (unsigned short)p;
+      }
+    }
+    __syncthreads();
+    const int nl = s_nlist;
+    if (tid < CLIP_LANES && tid < nl) {
+      const OBox K = make_box_trig(kb, s_trig + rk, Q);      // once per kept row, not once per pair                // one entry per lane of the first wave: the polygons of 64 clippings fill the LDS
+      for (int i = tid; i < nl; i += CLIP_LANES) {
+        const int p = s_list[i];
+        const int r = s_ord[p];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) a[c] = boxes[(size_t)r * 9 + c];
+        if ((float)box_iou3d_lds(a, make_box_trig(a, s_trig + r, Q), kb, K, &s_poly[0][tid], &s_poly[1][tid]) > iou_thr) s_dead[p] = 1;
+      }
+    }
+    cur = found + 1;
+    __syncthreads();                       // the flags and the list of this pass are settled before the next search
+  }
+  for (int k = nk + tid; k < topk; k += FILT_T) out[k] = -1;
+  if (tid == 0) ans_cnt[blockIdx.x] = nk;
+}
+extern "C" int es_ground_answers(const float* boxes, const float* scores, int P, int Q, float iou_thr, float score_thr, int topk,
+                                 int* ans_idx, int* ans_cnt, void* stream) {
+  if (P < 0 || Q < 0) return -5;
+  if (Q > GANS_MAX || P > 65535 || topk < 1 || topk > (Q > 1 ? Q : 1)) return -4;
+  if (P == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (Q == 0) {                            // no row, no answer: counts 0, every index -1
+    ES_TRY(hipMemsetAsync(ans_cnt, 0, (size_t)P * sizeof(int), st));
+    ES_TRY(hipMemsetAsync(ans_idx, 0xff, (size_t)P * topk * sizeof(int), st));
+    return 0;
+  }
+  const size_t sh = (size_t)6 * Q * sizeof(double);      // the trigonometry table: 48 KB at Q = 1024, next to 58 KB of static LDS
+  ES_TRY(hipFuncSetAttribute((const void*)k_ground_answers, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+  hipLaunchKernelGGL(k_ground_answers, dim3(P), dim3(FILT_T), sh, st, boxes, scores, Q, iou_thr, score_thr, topk, ans_idx, ans_cnt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ detection metric (IndoorDetMetric, eval/indoor_eval.py)
 // eval_det_cls:111-132,145-158: one lane per prediction walks the ground-truth boxes of its (scene, class) group in the scene's
 // order.  A prediction with a face below 2e-4 m^2 (f32 products) has its three sizes clamped to 2e-2 first; the IoU is the f64

@@ -15,7 +15,18 @@ compared in f32, like the score, against the f32 value of the threshold; a NaN I
 
 render=DIR (run_scene, walk_scene, --render): frame_0000.png ... = dscan['img'] -- the resized frames the image backbone saw -- under the
 prediction, projected with that sample's own depth2img matrices (frame_matrices), so the picture shows the projection the fusion used;
-legend.json (class name -> colour) lies next to them.  embodiedscan_amd.render draws on the device; with render=None nothing of it runs."""
+legend.json (class name -> colour) lies next to them.  embodiedscan_amd.render draws on the device; with render=None nothing of it runs.
+
+Asking in words (a grounding configuration):
+
+    python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S --prompt "the chair next to the window" [--prompt ...]
+                                         [--prompts-file F] [--topk K] [--iou-thr X] [--score-thr Y] [--walk] [--render DIR]
+
+ground_scene encodes the folder once and grounds every prompt on that encoding; ask_walk feeds a GroundWalk frame by frame and answers
+on the prefix seen so far.  select_answers turns the Q boxes and scores ground() returns per prompt into a short list of distinct boxes:
+the greedy of filter_instances with one class, for ALL prompts in one launch of es_ground_answers and one host read.  The JSON holds
+results = [{t, prompt, boxes, scores, keep}] (t: the last frame of the prefix, null for the whole recording); with --render every
+prompt's answers are drawn in the prompt's own colour (legend.json: prompt -> colour)."""
 import json
 import os
 
@@ -61,6 +72,65 @@ def filter_instances(instances, iou_thr=0.15, score_thr=0.075, topk_per_class=10
              P(keep_idx), P(keep_cnt), st)
     keep = keep_idx[:int(keep_cnt.item())].long()
     return InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(boxes[keep]), scores_3d=scores[keep], labels_3d=labels[keep], keep=keep)
+
+
+MAX_ANSWER_ROWS, MAX_ANSWER_PROMPTS = 1024, 65535      # limits of es_ground_answers
+
+
+def select_answers(results, iou_thr=0.25, score_thr=0.0, topk=1):
+    """what SparseFeatureFusion3DGrounder.ground returns -- a list of P InstanceData with Q rows each -- or stacked (boxes (P, Q, 9),
+    scores (P, Q)) tensors -> a list of P InstanceData(bboxes_3d, scores_3d, keep): per prompt the at most `topk` distinct boxes in
+    selection order (score descending, ties to the lower row; a row below score_thr or with a NaN score is never an answer; a row whose
+    9-DoF IoU with an already chosen one exceeds iou_thr is skipped), `keep` = int64 rows of the prompt's input.  ONE launch of
+    es_ground_answers for all prompts and one host read (the P counts).  The defaults are interface choices: 0.25 is the lower IoU at
+    which GroundingMetric calls two boxes the same object, topk = 1 is "the" answer.  ValueError before any launch: inputs on different
+    devices, prompts with different numbers of rows, more than 1024 rows or 65535 prompts, topk outside 1 .. max(Q, 1)."""
+    if isinstance(results, (tuple, list)) and len(results) == 2 and all(torch.is_tensor(t) for t in results):
+        boxes, scores = results
+        if boxes.dim() != 3 or boxes.shape[2] != 9 or tuple(scores.shape) != tuple(boxes.shape[:2]):
+            raise ValueError(f'select_answers: boxes (P, Q, 9), scores (P, Q); got {tuple(boxes.shape)}, {tuple(scores.shape)}')
+        if boxes.device != scores.device:
+            raise ValueError(f'select_answers: boxes on {boxes.device}, scores on {scores.device}')
+        n_p, n_q = int(boxes.shape[0]), int(boxes.shape[1])
+        per_b, per_s = list(boxes), list(scores)
+    else:
+        results = list(results)
+        per_b = [getattr(r.bboxes_3d, 'tensor', r.bboxes_3d) for r in results]
+        per_s = [r.scores_3d for r in results]
+        n_p = len(results)
+        devs = {t.device for t in per_b + per_s}
+        if len(devs) > 1:
+            raise ValueError(f'select_answers: inputs on different devices: {sorted(str(d) for d in devs)}')
+        for b, s in zip(per_b, per_s):
+            if b.dim() != 2 or b.shape[1] != 9 or tuple(s.shape) != (b.shape[0],):
+                raise ValueError(f'select_answers: per prompt boxes (Q, 9) and scores (Q); got {tuple(b.shape)}, {tuple(s.shape)}')
+        qs = {int(b.shape[0]) for b in per_b}
+        if len(qs) > 1:
+            raise ValueError(f'select_answers: the prompts carry different numbers of rows {sorted(qs)}; one launch takes one Q')
+        n_q = qs.pop() if qs else 0
+        boxes = torch.stack(per_b) if n_p else None
+        scores = torch.stack(per_s) if n_p else None
+    if n_q > MAX_ANSWER_ROWS:
+        raise ValueError(f'select_answers: {n_q} rows per prompt, the selection covers {MAX_ANSWER_ROWS}')
+    if n_p > MAX_ANSWER_PROMPTS:
+        raise ValueError(f'select_answers: {n_p} prompts, one launch covers {MAX_ANSWER_PROMPTS}')
+    topk = int(topk)
+    if not 1 <= topk <= max(n_q, 1):
+        raise ValueError(f'select_answers: topk = {topk} outside 1 .. {max(n_q, 1)} (Q = {n_q})')
+    if n_p == 0:
+        return []
+    dev, P = boxes.device, hip.P
+    b, s = boxes.float().contiguous(), scores.float().contiguous()
+    ans_idx = torch.empty((n_p, topk), dtype=torch.int32, device=dev)
+    ans_cnt = torch.empty(n_p, dtype=torch.int32, device=dev)
+    hip.call('es_ground_answers', P(b), P(s), n_p, n_q, float(iou_thr), float(score_thr), topk, P(ans_idx), P(ans_cnt), hip.stream())
+    counts = ans_cnt.tolist()                                            # the one host read
+    idx = ans_idx.long()
+    out = []
+    for p, c in enumerate(counts):
+        keep = idx[p, :c]
+        out.append(InstanceData(bboxes_3d=EulerDepthInstance3DBoxes(per_b[p][keep]), scores_3d=per_s[p][keep], keep=keep))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------ the folder
@@ -305,6 +375,127 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
         yield t, res
 
 
+# ------------------------------------------------------------------------------------------------------------------ asking in words
+def _is_grounder(detector):
+    return hasattr(detector, 'text_encoder') and hasattr(detector, 'ground')
+
+
+def _need_grounder(detector, fn):
+    if not _is_grounder(detector):
+        raise ValueError(f'{type(detector).__name__}: {fn} serves the grounding models (run_scene / walk_scene take the others)')
+
+
+def _prompt_texts(prompts):
+    texts = [p if isinstance(p, str) else p.text for p in prompts]
+    if not texts:
+        raise ValueError('at least one prompt is needed')
+    return texts
+
+
+def sweeps_pipeline(pipeline):
+    """the frame-ordered form of a transform list, as the cont-* configurations write it: AggregateMultiViewPoints(save_slices=True), no
+    top-level PointSample (it would re-draw the aggregated cloud over all frames, the ones not yet seen included), ConstructMultiSweeps
+    before the packing.  The cloud of such a scan is every frame's view sample, in frame order.  A list that already is one: unchanged."""
+    from .datasets.loading import ScanPipeline
+    if isinstance(pipeline, ScanPipeline) or any(t['type'].split('.')[-1] == 'ConstructMultiSweeps' for t in pipeline):
+        return pipeline
+    out = []
+    for t in pipeline:
+        ty = t['type'].split('.')[-1]
+        if ty == 'PointSample':
+            continue
+        if ty == 'Pack3DDetInputs':
+            out.append(dict(type='ConstructMultiSweeps'))
+        out.append(dict(t, save_slices=True) if ty == 'AggregateMultiViewPoints' else t)
+    if not any(t['type'].split('.')[-1] == 'ConstructMultiSweeps' for t in out):
+        out.append(dict(type='ConstructMultiSweeps'))
+    return out
+
+
+def prompt_palette(n):
+    """(n, 3) u8: row p = the colour of prompt p (render.class_palette without its grey row 0)"""
+    from . import render as RD
+    return RD.class_palette(n + 1)[1:]
+
+
+def draw_answers(frames, extrinsic, intrinsic, answers, palette_dev):
+    """the answers of every prompt (a list of InstanceData, one per prompt) over frames (V, 3, H, W) u8, each prompt's boxes in its own
+    colour -> (V, H, W, 3) u8 on the device"""
+    from . import render as RD
+    boxes = torch.cat([a.bboxes_3d.tensor.reshape(-1, 9) for a in answers])
+    colors = torch.cat([palette_dev[p:p + 1].expand(len(a.scores_3d), 3) for p, a in enumerate(answers)])
+    return RD.render_boxes(frames, extrinsic, intrinsic, boxes, colors.contiguous(), layout='chw')
+
+
+def _write_prompt_legend(dir, texts):
+    pal = prompt_palette(len(texts))
+    os.makedirs(dir, exist_ok=True)
+    with open(os.path.join(dir, 'legend.json'), 'w') as f:
+        json.dump({tx: [int(c) for c in pal[p]] for p, tx in enumerate(texts)}, f)
+    return pal
+
+
+def _selected(res, select):
+    return res if select is None else select_answers(res, **select)
+
+
+def ground_scene(detector, scene_dir, pipeline, prompts, seed=0, select=dict(), render=None):
+    """ask a recording in words: the folder is loaded and encoded ONCE (encode_scene), every prompt is grounded on that encoding and
+    select_answers makes the answers.  -> one InstanceData(bboxes_3d, scores_3d, keep) per prompt; select: keyword arguments of
+    select_answers, None: the raw result of ground() (Q rows per prompt).  render: a directory that receives every view of the scan
+    under the answers, one colour per PROMPT, as frame_0000.png ... and legend.json (prompt -> colour); None: nothing is drawn."""
+    from . import pipeline as PL
+    _need_grounder(detector, 'ground_scene')
+    texts = _prompt_texts(prompts)
+    dscan = load_scene(detector, scene_dir, pipeline, seed)
+    data = detector.data_preprocessor(PL.make_batch([dscan]), False)
+    scene = detector.encode_scene(data['inputs'], data['data_samples'])[0]
+    res = _selected(detector.ground(scene, prompts), select)
+    if render is not None:
+        from . import render as RD
+        pal = torch.from_numpy(_write_prompt_legend(render, texts)).to(detector.device)
+        E, K = frame_matrices(dscan)
+        RD.save_frames(render, draw_answers(dscan['img'], E, K, res, pal))
+    return res
+
+
+def ask_walk(detector, scene_dir, pipeline, prompts, seed=0, select=dict(), every=1, max_frames=None, render=None):
+    """generator over the frames of the folder: opens a GroundWalk, feeds it frame by frame (the frame-ordered form of the pipeline:
+    sweeps_pipeline) and, every `every` frames and behind the last one, yields (t, the answers per prompt for frames 0 .. t) -- the
+    questions are answered while the walk goes on, and a frame seen once is not paid for again.  select as in ground_scene.  render: a
+    directory that receives frame t under the answers of prefix t (the frames that yield) and legend.json; None: nothing is drawn."""
+    from . import pipeline as PL
+    _need_grounder(detector, 'ask_walk')
+    texts = _prompt_texts(prompts)
+    every = int(every)
+    if every < 1:
+        raise ValueError(f'ask_walk: every = {every}')
+    dscan = load_scene(detector, scene_dir, sweeps_pipeline(pipeline), seed)
+    batch = PL.make_batch([dscan])
+    cloud = batch['inputs']['points'][0]
+    data = detector.data_preprocessor(batch, False)
+    imgs = data['inputs']['imgs'].clone()                                # (the preprocessor's buffers are a ring)
+    meta = dict(data['data_samples'][0].metainfo)
+    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
+    meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
+    n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
+    walk = detector.open_walk(meta, max_frames=max(n_frames, 1))
+    if render is not None:
+        from . import render as RD
+        pal = torch.from_numpy(_write_prompt_legend(render, texts)).to(detector.device)
+        E, K = frame_matrices(dscan)
+    for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
+        if t >= n_frames:
+            break
+        walk.observe(imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
+        if (t + 1) % every and t + 1 != n_frames:
+            continue
+        res = _selected(walk.ask(prompts), select)
+        if render is not None:
+            RD.save_frames(render, draw_answers(dscan['img'][t:t + 1], E[t:t + 1], K[t:t + 1], res, pal), start=t)
+        yield t, res
+
+
 # ------------------------------------------------------------------------------------------------------------------ the command line
 def _class_names(cfg, n):
     mi = cfg.get('metainfo') or {}
@@ -321,6 +512,21 @@ def _record(res, names, **extra):
     return dict(extra, shape=list(res.shape), class_histogram=hist)
 
 
+def _answer_records(t, texts, answers):
+    return [dict(t=t, prompt=tx, boxes=a.bboxes_3d.tensor.cpu().tolist(), scores=a.scores_3d.cpu().tolist(), keep=a.keep.cpu().tolist())
+            for tx, a in zip(texts, answers)]
+
+
+def _emit(a, doc):
+    doc = json.dumps(doc)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(doc)
+    else:
+        print(doc)
+    return 0
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog='python -m embodiedscan_amd.inference', description=__doc__.split('\n\n')[0])
@@ -331,16 +537,41 @@ def main(argv=None):
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--walk', action='store_true', help='frame by frame through a walk session (continuous models)')
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--iou-thr', type=float, default=0.15)
-    ap.add_argument('--score-thr', type=float, default=0.075)
+    ap.add_argument('--iou-thr', type=float, default=None, help='default: 0.15 (object list), 0.25 (answers of a grounder)')
+    ap.add_argument('--score-thr', type=float, default=None, help='default: 0.075 (object list), 0.0 (answers of a grounder)')
     ap.add_argument('--topk-per-class', type=int, default=10)
+    ap.add_argument('--prompt', action='append', default=[], metavar='TEXT', help='a question for a grounding model (repeatable)')
+    ap.add_argument('--prompts-file', default=None, metavar='F', help='one prompt per line')
+    ap.add_argument('--topk', type=int, default=1, help='answers per prompt (grounding models)')
     ap.add_argument('--out', default=None, help='JSON file (default: standard output)')
     ap.add_argument('--render', default=None, metavar='DIR', help='write every frame under its prediction as DIR/frame_0000.png ... and DIR/legend.json')
     a = ap.parse_args(argv)
-    det, cfg = init_model(a.config, a.checkpoint, a.device)
+    prompts = list(a.prompt)
+    if a.prompts_file is not None:
+        with open(a.prompts_file) as f:
+            prompts += [ln.strip() for ln in f if ln.strip()]
+    from . import models  # noqa: F401  (fills the registry)
+    from .config import load_config
+    from .registry import MODELS
+    cfg = load_config(a.config)
+    grounder = hasattr(MODELS.get(cfg['model']['type']), 'ground')       # the class the configuration names: a grounding model?
+    if grounder and not prompts:                                         # (both refusals before the model is built)
+        ap.error(f"{cfg['model']['type']} grounds prompts: give --prompt TEXT (repeatable) or --prompts-file F")
+    if prompts and not grounder:
+        ap.error(f"{cfg['model']['type']} takes no prompt: --prompt / --prompts-file go with a grounding configuration")
+    det, cfg = init_model(cfg, a.checkpoint, a.device)
     scene_dir = os.path.join(a.root_dir, a.scene)
-    flt = dict(iou_thr=a.iou_thr, score_thr=a.score_thr, topk_per_class=a.topk_per_class)
     pipe = pipeline_of(cfg)
+    if grounder:
+        sel = dict(iou_thr=0.25 if a.iou_thr is None else a.iou_thr, score_thr=0.0 if a.score_thr is None else a.score_thr, topk=a.topk)
+        if a.walk:
+            results = [r for t, ans in ask_walk(det, scene_dir, pipe, prompts, a.seed, sel, render=a.render) for r in _answer_records(t, prompts, ans)]
+        else:
+            ans = ground_scene(det, scene_dir, pipe, prompts, a.seed, sel, render=a.render)
+            results = _answer_records(None, prompts, ans)                 # (t: the last frame of the prefix; null: the whole recording)
+        return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), select=sel, results=results))
+    flt = dict(iou_thr=0.15 if a.iou_thr is None else a.iou_thr, score_thr=0.075 if a.score_thr is None else a.score_thr,
+               topk_per_class=a.topk_per_class)
     kind = _kind(det)
     nc = getattr(det.bbox_head, 'num_classes', 0)
     names = _class_names(cfg, nc) if kind in ('det3d', 'cont-det3d') else ['empty'] + _class_names(cfg, max(nc - 1, 0))
@@ -348,14 +579,7 @@ def main(argv=None):
         results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names)]
     else:
         results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names))]
-    doc = json.dumps(dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt,
-                          results=results))
-    if a.out:
-        with open(a.out, 'w') as f:
-            f.write(doc)
-    else:
-        print(doc)
-    return 0
+    return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt, results=results))
 
 
 if __name__ == '__main__':

@@ -309,6 +309,13 @@ class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
             cut = [(nk['feats'].d[b * Lmax:b * Lmax + n].clone(), nk['points'][b * Lmax:b * Lmax + n].clone()) for b, n in enumerate(nk['lens'])]
         return [self.scene_from_tokens(f, p) for f, p in cut]
 
+    def open_walk(self, metainfo, max_frames=50):
+        """a session that takes a recording one frame at a time and answers prompts on the prefix seen so far (walk.GroundWalk):
+        walk.observe(img, points, depth2img) keeps the frame, walk.ask(prompts) grounds on everything observed.  The feature maps of up
+        to max_frames <= 64 frames stay on the device; ValueError above that"""
+        from .walk import GroundWalk
+        return GroundWalk(self, metainfo, max_frames)
+
     def ground(self, scene, prompts, tokens_positive=None, max_prompts=64):
         """InstanceData(bboxes_3d, scores_3d, target_scores_3d) per prompt -- what predict() attaches to a (scene, prompt) sample -- for
         any number of prompts on one encoded scene, Q = min(num_queries, L) rows each.  prompts: strings or objects with .text (and

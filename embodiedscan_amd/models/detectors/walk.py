@@ -1,4 +1,4 @@
-"""Walk sessions of the continuous models: frame in, prediction out.
+"""Walk sessions of the continuous models and of the grounder: frame in, prediction (or answers to prompts) out.
 
 EmbodiedOccPredictor.predict / Embodied3DDetector.predict take the whole walk (T frames, T cumulative clouds) and return T results.
 An agent that is walking has frame t only; a session (`detector.open_walk(metainfo)`) holds what frames 0 .. t-1 left behind and
@@ -11,15 +11,18 @@ DetWalk   the fusion of prefix t gathers every earlier view at the CURRENT voxel
           kept (preallocated for `max_frames` <= 64, the view limit of the window kernels) and the existing per-level window fusion runs
           on their first t + 1 views.
 
-Both re-voxelise the cloud so far and run the 3-D branch on it: those are exact, an incremental 3-D backbone is not.  Conventions follow
+GroundWalk (SparseFeatureFusion3DGrounder.open_walk) keeps the maps as DetWalk does, but its observe() does no 3-D work and returns the frame
+          count: scene() encodes the prefix so far (all t + 1 views, cached until the next observe) and ask(prompts) grounds on it.
+
+All re-voxelise the cloud so far and run the 3-D branch on it: those are exact, an incremental 3-D backbone is not.  Conventions follow
 the grounder's SceneEncoding: a session records engine.PRECISION[0] / engine.WEIGHT_VERSION[0] when it is opened and observe() raises
 ValueError once either has moved (the state was computed with other weights) or the device differs.  Every observe runs in eval mode
 with the tape off; the detector's `training` flag and engine.TAPE.enabled are restored afterwards and nothing is recorded.
 
 Failure: every refusal (stale weights, device, argument shapes, max_frames) comes before anything is launched and leaves the session as
-it was.  DetWalk commits a frame only when its prediction is made.  OccWalk commits it with the step launch, which moves the sum in
-place: an error raised behind that launch (3-D branch, neck, head) leaves the frame counted with no prediction returned -- reset() the
-walk then."""
+it was.  DetWalk commits a frame only when its prediction is made, GroundWalk when its observe has succeeded.  OccWalk commits it
+with the step launch, which moves the sum in place: an error raised behind that launch (3-D branch, neck, head) leaves the frame
+counted with no prediction returned -- reset() the walk then."""
 import torch
 from ... import engine as E
 from ... import hip
@@ -123,12 +126,15 @@ class _Walk:
         self.t = 0                       # frames observed so far
         self._frame = None               # (1, H, W, 3) f32: the image backbone's input, one stable address per session
 
-    def _check(self, img, points):
+    def _check_state(self):
         if self.precision != E.PRECISION[0] or self.weight_version != E.WEIGHT_VERSION[0]:
             raise ValueError(f'the walk was opened under precision {self.precision!r} / weight version {self.weight_version}, now '
                              f'{E.PRECISION[0]!r} / {E.WEIGHT_VERSION[0]}: its state is stale, open a new walk')
         if _device(self.det.device) != self.device:
             raise ValueError(f'the walk was opened on {self.device}, the detector now is on {self.det.device}')
+
+    def _check(self, img, points):
+        self._check_state()
         for name, t in (('img', img), ('points', points)):
             if _device(t.device) != self.device:
                 raise ValueError(f'{name} is on {t.device}, the walk on {self.device}')
@@ -223,10 +229,9 @@ class OccWalk(_Walk):
             return det.bbox_head.argmax(logits, dims)[0]
 
 
-class DetWalk(_Walk):
-    """Embodied3DDetector.open_walk(metainfo, max_frames).  observe() -> InstanceData(bboxes_3d, scores_3d, labels_3d) of the prefix so
-    far.  The feature maps of every observed frame stay on the device: per level one (max_frames Hf Wf, C) buffer in the dtype the
-    backbone emits (allocated at the first observe, when the map sizes are known)."""
+class _MapWalk(_Walk):
+    """a session that keeps the four levels' feature maps of every observed frame on the device: per level one (max_frames Hf Wf, C)
+    buffer in the dtype the backbone emits (allocated at the first observe, when the map sizes are known)"""
 
     def __init__(self, det, metainfo, max_frames=50):
         max_frames = int(max_frames)
@@ -257,6 +262,15 @@ class DetWalk(_Walk):
         for (m, Hf, Wf), (f, _, _) in zip(self.maps, img_feats):
             m[t * Hf * Wf:(t + 1) * Hf * Wf].copy_(f.d)
 
+    def _views(self, k):
+        """the maps of the first k frames, as the fusion takes them"""
+        return [(E.Var(m[:k * Hf * Wf], rg=False), Hf, Wf) for m, Hf, Wf in self.maps]
+
+
+class DetWalk(_MapWalk):
+    """Embodied3DDetector.open_walk(metainfo, max_frames).  observe() -> InstanceData(bboxes_3d, scores_3d, labels_3d) of the prefix so
+    far.  The feature maps of every observed frame stay on the device (_MapWalk)."""
+
     def observe(self, img, points, depth2img):
         self._check(img, points)
         if self.t >= self.max_frames:
@@ -278,7 +292,7 @@ class DetWalk(_Walk):
                 else:
                     self._keep_maps(img_feats)
                 n = self.cloud.append(points)
-                views = [(E.Var(m[:(t + 1) * Hf * Wf], rg=False), Hf, Wf) for m, Hf, Wf in self.maps]
+                views = self._views(t + 1)
                 sample = Det3DDataSample(self.meta.metainfo())
                 det._win_t0 = t                          # the one batch entry of the launch is prefix t: window = views 0 .. t
                 x = det._fuse_points({'points': [self.cloud.buf[:n]]}, [sample], (views, t + 1, hw, forked))
@@ -291,3 +305,84 @@ class DetWalk(_Walk):
             self.cloud.n = n
             self.t = t + 1
             return res
+
+
+class GroundWalk(_MapWalk):
+    """SparseFeatureFusion3DGrounder.open_walk(metainfo, max_frames): ask a recording in words while it is being walked.
+
+    observe() runs the 2-D backbone on the one frame, keeps its four maps and appends the frame's rows to the cloud -- no 3-D work -- and
+    returns the number of frames seen.  scene() is the SceneEncoding of the prefix so far: the fusion of the cloud so far with views
+    0 .. t (all V = t + 1 of them, the base _fuse_level), MinkNeck and scene_from_tokens; it is cached until the next observe, so
+    any number of ask() calls between two frames pay for the 3-D branch once.  ask(prompts) = det.ground(scene(), prompts); with any of
+    iou_thr / score_thr / topk the result goes through inference.select_answers.
+
+    Failure: as on the siblings every refusal comes before anything is launched and leaves the session as it was; a frame is committed
+    only when its observe has succeeded (the map rows and cloud rows an interrupted observe wrote lie behind the committed ones and
+    are overwritten by the next)."""
+
+    def __init__(self, det, metainfo, max_frames=50):
+        super().__init__(det, metainfo, max_frames)
+        self._scene = None               # SceneEncoding of the prefix 0 .. t-1, None: not built since the last observe
+        self._hw = None
+
+    def reset(self):
+        super().reset()
+        self._scene = None
+
+    def observe(self, img, points, depth2img):
+        self._check(img, points)
+        if self.t >= self.max_frames:
+            raise ValueError(f'the walk was opened for max_frames = {self.max_frames} frames and has seen them all')
+        WalkMeta._frame(depth2img)
+        det = self.det
+        n = self.cloud.append(points)                    # (a cloud with other columns is refused here, before the backbone runs)
+        with self._guard():
+            hip.refresh_stream()
+            det._bind()
+            H, W = self._stage_frame(img)
+            img5 = self._frame.view(1, 1, H, W, 3).permute(0, 1, 4, 2, 3)
+            img_feats, _, hw, forked = det._image_feats(img5)
+            self._alloc_maps(img_feats)                  # (on the main stream: the buffers outlive every side-stream segment)
+            if forked:                                   # the copies ride behind the image backbone on its stream
+                with E.side_stream(fork=False):
+                    self._keep_maps(img_feats)
+                E.join_side()                            # whatever the caller queues next sees the maps
+            else:
+                self._keep_maps(img_feats)
+        self.meta.add(depth2img)
+        self.cloud.n = n
+        self._hw = hw
+        self._scene = None
+        self.t += 1
+        return self.t
+
+    def scene(self):
+        """the SceneEncoding of the frames observed so far (the same object until the next observe)"""
+        self._check_state()
+        if self.t == 0:
+            raise ValueError('the walk has not observed a frame yet: nothing to encode')
+        if self._scene is not None:
+            return self._scene
+        det, t = self.det, self.t
+        with self._guard():
+            hip.refresh_stream()
+            det._bind()
+            sample = Det3DDataSample(self.meta.metainfo())
+            det.start_tape_parts()                       # (what _image_feats leaves behind for _fuse_points; nothing is recorded here)
+            det._branch_ends = [len(E.TAPE.fns), None]
+            x = det._fuse_points({'points': [self.cloud.buf[:self.cloud.n]]}, [sample], (self._views(t), t, self._hw, False))
+            det.neck_3d(x, 1)
+            nk = det.neck_3d.last
+            L = nk['lens'][0]
+            feats, points = nk['feats'].d[:L].clone(), nk['points'][:L].clone()
+        self._scene = det.scene_from_tokens(feats, points)
+        return self._scene
+
+    def ask(self, prompts, tokens_positive=None, **select):
+        """InstanceData per prompt for the prefix so far: what det.ground returns (Q rows each), or -- with iou_thr / score_thr / topk --
+        the answers inference.select_answers makes of it"""
+        res = self.det.ground(self.scene(), prompts, tokens_positive)
+        if select:
+            from ...inference import select_answers
+            res = select_answers(res, **select)
+        return res

@@ -606,6 +606,16 @@ int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int M, float* 
  * -4, nothing written: n > 16384 (es_topk_sorted's limit), n_classes outside 1 .. 4096, topk_per_class < 1; -5: n < 0. */
 int es_box3d_iou_filter(const float* boxes, const float* scores, const int* labels, const int* order, int n, int n_classes,
                         float iou_thr, float score_thr, int topk_per_class, int* keep_idx, int* keep_cnt, void* stream);
+/* The answers of a grounder, all prompts in ONE launch (grid = P, one workgroup per prompt; no sorted order is passed in):
+ * boxes (P,Q,9), scores (P,Q).  Per prompt, independently, the greedy of es_box3d_iou_filter with one class: rows by descending
+ * score (ties to the lower row, -0.0 ties with +0.0); a row with score < score_thr (f32) or a NaN score is never an answer; a row
+ * is skipped when iou(row, j) > iou_thr for any kept row j (the [row][j] element es_box3d_iou stores, f32 compare, a NaN IoU does
+ * not suppress); the walk stops at topk kept rows.  ans_idx (P,topk): the kept rows of prompt p in selection order, -1 behind
+ * ans_cnt[p] -- every entry is written; ans_cnt (P).  P = 0: nothing is launched.  Q = 0: every count 0, every index -1.
+ * 58 KB of static LDS + 48 Q bytes of dynamic LDS per workgroup, no scratch.
+ * -4, nothing written: Q > 1024, topk < 1, topk > max(Q, 1), P > 65535; -5: P < 0 or Q < 0. */
+int es_ground_answers(const float* boxes, const float* scores, int P, int Q, float iou_thr, float score_thr, int topk, int* ans_idx,
+                      int* ans_cnt, void* stream);
 /* N5: IndoorDetMetric on the device (embodiedscan/eval/indoor_eval.py:8-182).  Ground-truth rows are ordered by (scene, class)
  * group, grp_off_dev (n_grp+1) delimits the groups, pred_grp (P) is a prediction's group or -1.
  * es_det_best_gt: predictions with a face below 2e-4 have their sizes clamped to 2e-2; iou_max (P) = the highest f64 polyhedral IoU
