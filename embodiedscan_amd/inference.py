@@ -34,6 +34,8 @@ import numpy as np
 import torch
 
 from . import hip
+from . import pipeline as PL
+from . import render as RD
 from .structures import EulerDepthInstance3DBoxes, InstanceData
 
 MAX_ROWS, MAX_CLASSES = 16384, 4096          # limits of es_topk_sorted / es_box3d_iou_filter
@@ -221,23 +223,14 @@ def pipeline_of(cfg):
 
 
 def _kind(detector):
-    from .models.detectors.dense_fusion_occ import DenseFusionOccPredictor
-    from .models.detectors.embodied_det3d import Embodied3DDetector
-    from .models.detectors.embodied_occ import EmbodiedOccPredictor
-    if isinstance(detector, EmbodiedOccPredictor):
-        return 'cont-occ'
-    if isinstance(detector, Embodied3DDetector):
-        return 'cont-det3d'
-    if isinstance(detector, DenseFusionOccPredictor):
-        return 'occ'
-    if hasattr(getattr(detector, 'bbox_head', None), 'num_classes') and not hasattr(detector, 'text_encoder'):
-        return 'det3d'
+    """'det3d' / 'occ', 'cont-' in front for the continuous models: from the class attributes `task` and `continuous`"""
+    if getattr(detector, 'task', None) in ('det3d', 'occ'):
+        return ('cont-' if detector.continuous else '') + detector.task
     raise ValueError(f'{type(detector).__name__}: run_scene / walk_scene serve the detection and occupancy models (a grounder needs a prompt)')
 
 
 def load_scene(detector, scene_dir, pipeline, seed=0):
     """scene_info -> ScanPipeline.from_cfg(pipeline) with numpy RandomState(seed) -> the scan on the detector's device"""
-    from . import pipeline as PL
     from .datasets.loading import ScanPipeline
     scan = ScanPipeline.from_cfg(pipeline)(scene_info(scene_dir), np.random.RandomState(seed))
     return PL.upload_scan(scan, detector.device)
@@ -245,18 +238,12 @@ def load_scene(detector, scene_dir, pipeline, seed=0):
 
 def make_scene_batch(detector, dscan):
     """the batch builder of the detector's kind on a scan without ground truth (the continuous kinds: one cloud per prefix)"""
-    from . import pipeline as PL
     kind = _kind(detector)
     if kind == 'cont-det3d':
         return PL.make_cont_det_batch(dscan)
-    if kind == 'cont-occ':
-        data = PL.make_batch([dscan])
-        pts = data['inputs']['points'][0]
-        data['inputs']['points'] = [pts[:e] for e in PL.prefix_lengths(dscan['points_slice_indices'], pts.shape[0])]
-        ds = data['data_samples'][0]
-        ds.gt_occupancy = torch.zeros((0, 4), dtype=torch.int64)
-        ds.gt_occupancy_masks = [None] * len(data['inputs']['points'])      # (per prefix: what makes the preprocessor split the sample)
-        return data
+    if kind == 'cont-occ':                                               # (one mask per prefix makes the preprocessor split the sample)
+        return PL.make_cont_occ_batch(dscan, dict(gt_occupancy=torch.zeros((0, 4), dtype=torch.int64),
+                                                  gt_occupancy_masks=[None] * (len(dscan['points_slice_indices']) - 1)))
     return PL.make_batch([dscan])
 
 
@@ -267,8 +254,7 @@ def frame_matrices(dscan):
     intrinsic's first two rows.  ValueError for a scan whose pipeline flipped / cropped the image or moved the cloud (a train-time
     augmentation: its predictions do not live in the aligned frame)."""
     meta = dscan['meta']
-    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
-    pm = meta[key]
+    pm = meta[PL.projection_key(meta)]
     E = np.stack([np.asarray(e, np.float64) for e in pm['extrinsic']])
     intr = pm['intrinsic']
     K = np.stack([np.asarray(k, np.float64) for k in intr]) if isinstance(intr, (list, tuple)) else np.repeat(np.asarray(intr, np.float64)[None], len(E), 0)
@@ -291,29 +277,43 @@ def _default_names(detector, kind):
 
 def scene_palette(detector):
     """(n_classes, 3) u8: row l = the colour of label l.  Detectors skip render.class_palette's grey row 0; occupancy keeps it for `empty`"""
-    from . import render as RD
     kind, nc = _kind(detector), int(getattr(detector.bbox_head, 'num_classes', 0))
     return RD.class_palette(nc + 1)[1:] if kind in ('det3d', 'cont-det3d') else RD.class_palette(max(nc, 1))
 
 
 def draw_prediction(detector, frames, extrinsic, intrinsic, res, palette_dev):
     """one prediction (InstanceData or an (X, Y, Z) volume) over frames (V, 3, H, W) u8 -> (V, H, W, 3) u8 on the device"""
-    from . import render as RD
     if isinstance(res, InstanceData):
         labels = res.labels_3d.long().clamp(0, palette_dev.shape[0] - 1)
         return RD.render_boxes(frames, extrinsic, intrinsic, res.bboxes_3d, palette_dev[labels], layout='chw')
     return RD.render_occupancy(frames, extrinsic, intrinsic, res, detector.point_cloud_range, palette_dev, layout='chw')
 
 
-def _write_legend(dir, detector, class_names):
-    kind = _kind(detector)
+def _class_legend(detector, class_names):
+    """-> (the name of every palette row, scene_palette): class_names cut or padded with class_<i> to the palette"""
     pal = scene_palette(detector)
-    names = list(class_names) if class_names is not None else _default_names(detector, kind)
-    names = names[:len(pal)] + [f'class_{i}' for i in range(len(names), len(pal))]
+    names = list(class_names) if class_names is not None else _default_names(detector, _kind(detector))
+    return names[:len(pal)] + [f'class_{i}' for i in range(len(names), len(pal))], pal
+
+
+def _painter(dir, names, palette, dscan, device, draw):
+    """writes dir/legend.json (names[i] -> palette[i]) now -> paint(res, t=None): draw(frames, extrinsic, intrinsic, res, palette on
+    the device) over frame t of the scan saved as frame_<t>.png; t None: over all its frames, numbered from 0"""
     os.makedirs(dir, exist_ok=True)
     with open(os.path.join(dir, 'legend.json'), 'w') as f:
-        json.dump({nm: [int(c) for c in pal[i]] for i, nm in enumerate(names)}, f)
-    return pal
+        json.dump({nm: [int(c) for c in palette[i]] for i, nm in enumerate(names)}, f)
+    pal = torch.from_numpy(palette).to(device)
+    E, K = frame_matrices(dscan)
+
+    def paint(res, t=None):
+        v = slice(None) if t is None else slice(t, t + 1)
+        RD.save_frames(dir, draw(dscan['img'][v], E[v], K[v], res, pal), start=t or 0)
+    return paint
+
+
+def _prediction_painter(dir, detector, class_names, dscan):
+    return _painter(dir, *_class_legend(detector, class_names), dscan, detector.device,
+                    lambda *args: draw_prediction(detector, *args))
 
 
 def _filtered(detector, inst, filter):
@@ -336,52 +336,52 @@ def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None,
     else:
         res = [_filtered(detector, ds.pred_instances_3d, filter) for ds in out]
     if render is not None:
-        from . import render as RD
-        pal = torch.from_numpy(_write_legend(render, detector, class_names)).to(detector.device)
-        E, K = frame_matrices(dscan)
-        RD.save_frames(render, draw_prediction(detector, dscan['img'], E, K, res[-1], pal))
+        _prediction_painter(render, detector, class_names, dscan)(res[-1])
     return res
+
+
+def _scene_walk(detector, dscan, batch, max_frames, capped):
+    """opens a walk session on the scan's constant meta (its projection entry without the matrices) -> (walk, n_frames, frames):
+    n_frames = min(max_frames, the scan's frames); frames yields (t, (img, rows, matrices)), the arguments of walk.observe for frame
+    t < n_frames.  capped: the session keeps per-frame maps and is opened for n_frames of them."""
+    cloud = batch['inputs']['points'][-1]
+    data = detector.data_preprocessor(batch, False)
+    imgs = data['inputs']['imgs'].clone()                                # (the preprocessor's buffers are a ring)
+    meta = dict(data['data_samples'][0].metainfo)
+    key = PL.projection_key(meta)
+    meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
+    n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
+    walk = detector.open_walk(meta, max_frames=max(n_frames, 1)) if capped else detector.open_walk(meta)
+
+    def frames():
+        for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
+            if t >= n_frames:
+                break
+            yield t, (imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
+    return walk, n_frames, frames()
 
 
 def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None):
     """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene): opens a walk
     session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy).  render: a directory that receives
     frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn."""
-    from . import pipeline as PL
     kind = _kind(detector)
     if kind not in ('cont-det3d', 'cont-occ'):
         raise ValueError(f'{type(detector).__name__} has no walk session: use run_scene')
     dscan = load_scene(detector, scene_dir, pipeline, seed)
-    batch = make_scene_batch(detector, dscan)
-    cloud = batch['inputs']['points'][-1]
-    data = detector.data_preprocessor(batch, False)
-    imgs = data['inputs']['imgs'].clone()                                # (the preprocessor's buffers are a ring)
-    meta = dict(data['data_samples'][0].metainfo)
-    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
-    meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
-    n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
-    walk = detector.open_walk(meta, max_frames=max(n_frames, 1)) if kind == 'cont-det3d' else detector.open_walk(meta)
-    if render is not None:
-        from . import render as RD
-        pal = torch.from_numpy(_write_legend(render, detector, class_names)).to(detector.device)
-        E, K = frame_matrices(dscan)
-    for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
-        if t >= n_frames:
-            break
-        res = walk.observe(imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
+    walk, _, frames = _scene_walk(detector, dscan, make_scene_batch(detector, dscan), max_frames, capped=kind == 'cont-det3d')
+    paint = None if render is None else _prediction_painter(render, detector, class_names, dscan)
+    for t, frame in frames:
+        res = walk.observe(*frame)
         res = res if kind == 'cont-occ' else _filtered(detector, res, filter)
-        if render is not None:
-            RD.save_frames(render, draw_prediction(detector, dscan['img'][t:t + 1], E[t:t + 1], K[t:t + 1], res, pal), start=t)
+        if paint is not None:
+            paint(res, t)
         yield t, res
 
 
 # ------------------------------------------------------------------------------------------------------------------ asking in words
-def _is_grounder(detector):
-    return hasattr(detector, 'text_encoder') and hasattr(detector, 'ground')
-
-
 def _need_grounder(detector, fn):
-    if not _is_grounder(detector):
+    if getattr(detector, 'task', None) != 'ground':
         raise ValueError(f'{type(detector).__name__}: {fn} serves the grounding models (run_scene / walk_scene take the others)')
 
 
@@ -414,25 +414,19 @@ def sweeps_pipeline(pipeline):
 
 def prompt_palette(n):
     """(n, 3) u8: row p = the colour of prompt p (render.class_palette without its grey row 0)"""
-    from . import render as RD
     return RD.class_palette(n + 1)[1:]
 
 
 def draw_answers(frames, extrinsic, intrinsic, answers, palette_dev):
     """the answers of every prompt (a list of InstanceData, one per prompt) over frames (V, 3, H, W) u8, each prompt's boxes in its own
     colour -> (V, H, W, 3) u8 on the device"""
-    from . import render as RD
     boxes = torch.cat([a.bboxes_3d.tensor.reshape(-1, 9) for a in answers])
     colors = torch.cat([palette_dev[p:p + 1].expand(len(a.scores_3d), 3) for p, a in enumerate(answers)])
     return RD.render_boxes(frames, extrinsic, intrinsic, boxes, colors.contiguous(), layout='chw')
 
 
-def _write_prompt_legend(dir, texts):
-    pal = prompt_palette(len(texts))
-    os.makedirs(dir, exist_ok=True)
-    with open(os.path.join(dir, 'legend.json'), 'w') as f:
-        json.dump({tx: [int(c) for c in pal[p]] for p, tx in enumerate(texts)}, f)
-    return pal
+def _answer_painter(dir, detector, texts, dscan):
+    return _painter(dir, texts, prompt_palette(len(texts)), dscan, detector.device, draw_answers)
 
 
 def _selected(res, select):
@@ -444,7 +438,6 @@ def ground_scene(detector, scene_dir, pipeline, prompts, seed=0, select=dict(), 
     select_answers makes the answers.  -> one InstanceData(bboxes_3d, scores_3d, keep) per prompt; select: keyword arguments of
     select_answers, None: the raw result of ground() (Q rows per prompt).  render: a directory that receives every view of the scan
     under the answers, one colour per PROMPT, as frame_0000.png ... and legend.json (prompt -> colour); None: nothing is drawn."""
-    from . import pipeline as PL
     _need_grounder(detector, 'ground_scene')
     texts = _prompt_texts(prompts)
     dscan = load_scene(detector, scene_dir, pipeline, seed)
@@ -452,10 +445,7 @@ def ground_scene(detector, scene_dir, pipeline, prompts, seed=0, select=dict(), 
     scene = detector.encode_scene(data['inputs'], data['data_samples'])[0]
     res = _selected(detector.ground(scene, prompts), select)
     if render is not None:
-        from . import render as RD
-        pal = torch.from_numpy(_write_prompt_legend(render, texts)).to(detector.device)
-        E, K = frame_matrices(dscan)
-        RD.save_frames(render, draw_answers(dscan['img'], E, K, res, pal))
+        _answer_painter(render, detector, texts, dscan)(res)
     return res
 
 
@@ -464,35 +454,21 @@ def ask_walk(detector, scene_dir, pipeline, prompts, seed=0, select=dict(), ever
     sweeps_pipeline) and, every `every` frames and behind the last one, yields (t, the answers per prompt for frames 0 .. t) -- the
     questions are answered while the walk goes on, and a frame seen once is not paid for again.  select as in ground_scene.  render: a
     directory that receives frame t under the answers of prefix t (the frames that yield) and legend.json; None: nothing is drawn."""
-    from . import pipeline as PL
     _need_grounder(detector, 'ask_walk')
     texts = _prompt_texts(prompts)
     every = int(every)
     if every < 1:
         raise ValueError(f'ask_walk: every = {every}')
     dscan = load_scene(detector, scene_dir, sweeps_pipeline(pipeline), seed)
-    batch = PL.make_batch([dscan])
-    cloud = batch['inputs']['points'][0]
-    data = detector.data_preprocessor(batch, False)
-    imgs = data['inputs']['imgs'].clone()                                # (the preprocessor's buffers are a ring)
-    meta = dict(data['data_samples'][0].metainfo)
-    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
-    meta[key] = {k: v for k, v in meta[key].items() if k not in ('extrinsic', 'intrinsic')}
-    n_frames = imgs.shape[1] if max_frames is None else min(int(max_frames), imgs.shape[1])
-    walk = detector.open_walk(meta, max_frames=max(n_frames, 1))
-    if render is not None:
-        from . import render as RD
-        pal = torch.from_numpy(_write_prompt_legend(render, texts)).to(detector.device)
-        E, K = frame_matrices(dscan)
-    for t, (r0, r1), e, i in PL.walk_frames(dscan, cloud.shape[0]):
-        if t >= n_frames:
-            break
-        walk.observe(imgs[0, t], cloud[r0:r1], dict(extrinsic=e, intrinsic=i))
+    walk, n_frames, frames = _scene_walk(detector, dscan, PL.make_batch([dscan]), max_frames, capped=True)
+    paint = None if render is None else _answer_painter(render, detector, texts, dscan)
+    for t, frame in frames:
+        walk.observe(*frame)
         if (t + 1) % every and t + 1 != n_frames:
             continue
         res = _selected(walk.ask(prompts), select)
-        if render is not None:
-            RD.save_frames(render, draw_answers(dscan['img'][t:t + 1], E[t:t + 1], K[t:t + 1], res, pal), start=t)
+        if paint is not None:
+            paint(res, t)
         yield t, res
 
 
@@ -554,7 +530,7 @@ def main(argv=None):
     from .config import load_config
     from .registry import MODELS
     cfg = load_config(a.config)
-    grounder = hasattr(MODELS.get(cfg['model']['type']), 'ground')       # the class the configuration names: a grounding model?
+    grounder = getattr(MODELS.get(cfg['model']['type']), 'task', None) == 'ground'   # the class the configuration names: a grounding model?
     if grounder and not prompts:                                         # (both refusals before the model is built)
         ap.error(f"{cfg['model']['type']} grounds prompts: give --prompt TEXT (repeatable) or --prompts-file F")
     if prompts and not grounder:

@@ -19,9 +19,12 @@ from ...sparse import SparseTensor
 from ..layers.fusion_layers.point_fusion import build_fusion_meta
 from .base import DetectorBase
 
+C3 = 512                     # channels of MinkResNet34's last level: columns [C2, C2 + C3) of the volume buffer
 
 @MODELS.register_module()
 class DenseFusionOccPredictor(DetectorBase):
+    task, continuous = 'occ', False
+
     def __init__(self, backbone, backbone_3d, neck, neck_3d, bbox_head, prior_generator, n_voxels, coord_type,
                  use_valid_mask=True, use_xyz_feat=False, point_cloud_range=None, train_cfg=None, test_cfg=None,
                  data_preprocessor=None, init_cfg=None, seed=0, device='cuda:0'):
@@ -86,51 +89,84 @@ class DenseFusionOccPredictor(DetectorBase):
             p = p + torch.as_tensor(origin, dtype=torch.float32)
         return p
 
+    def _batch_rule(self, B, V, points, batch_data_samples):
+        """refuses a batch this class cannot take (before anything is launched) -> (volumes the neck sees, the metas of the image samples)"""
+        assert B == 1, 'only support batch_size=1 here (dense_fusion_occ.py:160,251)'
+        return B, [ds.metainfo for ds in batch_data_samples]
+
+    def _project(self, f2d, Hf, Wf, prior, meta_dev, V, vol):
+        """the prior voxel centres into every view: the mean of the views' features into columns [0, C2) of `vol`.  Returns
+        bwd(g, acc): the gradient rows `g` of `vol` gathered back into f2d.g (acc 0: the gather overwrites it)."""
+        nvox, C2, ld = prior.shape[0], f2d.d.shape[1], vol.shape[1]
+        bidx = torch.zeros((nvox, 4), dtype=torch.int32, device=self.device)            # column 0 = sample index (0: B == 1)
+        pix = torch.empty((nvox, V), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(nvox, dtype=torch.int32, device=self.device)
+        call('es_point_sample_fwd_pts', P(bidx), P(prior), nvox, P(meta_dev), meta_dev.shape[1], V, P(f2d.d), Hf, Wf, C2,
+             P(vol), ld, P(pix), P(cnt), hip.stream())
+        E.mark('image volume (projection)')
+
+        def bwd(g, acc):
+            head = torch.empty(f2d.d.shape[0], dtype=torch.int32, device=self.device)
+            nxt = torch.empty(nvox * V, dtype=torch.int32, device=self.device)
+            call('es_point_sample_bwd', P(bidx), nvox, V, P(g), ld, P(pix), P(cnt), Hf, Wf, C2, P(f2d.g), V, P(head), P(nxt), acc,
+                 hip.stream())
+        return bwd
+
+    def image_maps(self, img):
+        """(B, V, 3, H, W) frames -> FPN level 0 of the B V views: (Var (B V Hf Wf, C2), Hf, Wf).  A frame block that already lies
+        channels-last in memory (a walk's staged frame) is taken as it is."""
+        B, V = img.shape[:2]
+        H, W = img.shape[-2:]
+        if img.stride(2) != 1:
+            img = img.permute(0, 1, 3, 4, 2).contiguous().permute(0, 1, 4, 2, 3)
+        nhwc = img.permute(0, 1, 3, 4, 2).reshape(B * V, H, W, 3)
+        E.refresh_weight_copies()
+        return self.neck(self.backbone(nhwc), B * V, levels=[0])[0]
+
+    def point_branch(self, clouds, vol, C2, rows=None, on_backbone=None):
+        """voxelise `clouds` (one batch entry each), MinkResNet on the xyz rows, its last level (stride 64 = one voxel of the volume)
+        scattered into columns [C2, C2 + C3) of `vol` (SparseTensor.dense()) -> (x3, didx = the volume row of every x3 row).  `rows`:
+        the clouds' rows in batch order as ONE tensor, from which the xyz features are gathered by its own row stride -- a walk passes
+        the buffer that holds its one cloud; None: a packed (n, 3) copy is made here.  on_backbone: called right behind the 3-D
+        backbone (the tape mark of a loss forward)."""
+        X, Y, Z = self.n_voxels
+        rmin = self.point_cloud_range[:3]
+        cmax = [n * self.voxel_stride - 1 for n in self.n_voxels]
+        cs, src = sparse.voxelize_range(clouds, rmin, self.voxel_size, cmax)
+        if rows is None:
+            rows = torch.cat([p[:, :3] for p in clouds]) if len(clouds) > 1 else clouds[0][:, :3].contiguous()
+        feats = torch.empty((cs.n, 3), dtype=torch.float32, device=self.device)
+        call('es_row_move', P(feats), 3, P(rows), rows.stride(0), P(src), cs.n, 3, 0, hip.stream())
+        x3 = self.backbone_3d(SparseTensor(cs, E.Var(feats, rg=False)))[-1]
+        if on_backbone is not None:
+            on_backbone()
+        assert x3.F.d.shape[1] == C3 and x3.cs.ts == self.voxel_stride
+        didx = torch.empty(x3.cs.n, dtype=torch.int32, device=self.device)
+        call('es_dense_index', P(x3.cs.coords), x3.cs.n, x3.cs.ts, X, Y, Z, P(didx), hip.stream())
+        call('es_row_move', vol.data_ptr() + 4 * C2, C2 + C3, P(x3.F.d), C3, P(didx), x3.cs.n, C3, 2, hip.stream())
+        return x3, didx
+
     def extract_feat(self, batch_inputs_dict, batch_data_samples):
-        """dense_fusion_occ.py:120-259.  Returns [(Var (X_i*Y_i*Z_i, 128), (X_i, Y_i, Z_i))] fine -> coarse."""
+        """dense_fusion_occ.py:120-259 (EmbodiedOccPredictor: embodied_occ.py:118-247, n = T prefix-major volumes).
+        Returns [(Var (n*X_i*Y_i*Z_i, 128), (X_i, Y_i, Z_i))] fine -> coarse."""
         self._bind()
         self.start_tape_parts()
         img = batch_inputs_dict['imgs']
         B, V = img.shape[:2]
         H, W = img.shape[-2:]
-        assert B == 1, 'only support batch_size=1 here (dense_fusion_occ.py:160,251)'
-        if img.stride(2) != 1:
-            img = img.permute(0, 1, 3, 4, 2).contiguous().permute(0, 1, 4, 2, 3)
-        nhwc = img.permute(0, 1, 3, 4, 2).reshape(B * V, H, W, 3)
-        E.refresh_weight_copies()
-        f2d, Hf, Wf = self.neck(self.backbone(nhwc), B * V, levels=[0])[0]
+        n, metas = self._batch_rule(B, V, batch_inputs_dict['points'], batch_data_samples)
+        f2d, Hf, Wf = self.image_maps(img)
         E.mark('2-D backbone + FPN')
         self.tape_part(1)                       # behind this point: 3-D backbone, then the neck parts
-        metas = [ds.metainfo for ds in batch_data_samples]
         X, Y, Z = self.n_voxels
-        nvox = X * Y * Z
         origin = metas[0]['depth2img'].get('origin') if isinstance(metas[0].get('depth2img'), dict) else None
         prior = self.prior_points(origin).to(self.device, non_blocking=True)
         meta_dev = build_fusion_meta(metas, self.coord_type, (H, W), V).to(self.device, non_blocking=True)
         C2 = f2d.d.shape[1]
-        C3 = 512
-        vol = torch.zeros((B * nvox, C2 + C3), dtype=torch.float32, device=self.device)
-        bidx = torch.zeros((B * nvox, 4), dtype=torch.int32, device=self.device)       # column 0 = sample index
-        pix = torch.empty((B * nvox, V), dtype=torch.int32, device=self.device)
-        cnt = torch.empty(B * nvox, dtype=torch.int32, device=self.device)
-        call('es_point_sample_fwd_pts', P(bidx), P(prior), B * nvox, P(meta_dev), meta_dev.shape[1], V, P(f2d.d), Hf, Wf, C2,
-             P(vol), C2 + C3, P(pix), P(cnt), hip.stream())
-        E.mark('image volume (projection)')
-        # sparse branch
+        vol = torch.zeros((n * X * Y * Z, C2 + C3), dtype=torch.float32, device=self.device)
+        project_bwd = self._project(f2d, Hf, Wf, prior, meta_dev, V, vol)
         pts = [p if (p.dtype == torch.float32 and p.stride(-1) == 1) else p.float().contiguous() for p in batch_inputs_dict['points']]
-        rmin = self.point_cloud_range[:3]
-        cmax = [n * self.voxel_stride - 1 for n in self.n_voxels]
-        cs, src = sparse.voxelize_range(pts, rmin, self.voxel_size, cmax)
-        allp = torch.cat([p[:, :3] for p in pts]) if len(pts) > 1 else pts[0][:, :3].contiguous()
-        feats = torch.empty((cs.n, 3), dtype=torch.float32, device=self.device)
-        call('es_row_move', P(feats), 3, P(allp), allp.stride(0), P(src), cs.n, 3, 0, hip.stream())
-        x3 = self.backbone_3d(SparseTensor(cs, E.Var(feats, rg=False)))[-1]
-        self.tape_part(2)
-        assert x3.F.d.shape[1] == C3 and x3.cs.ts == self.voxel_stride
-        didx = torch.empty(x3.cs.n, dtype=torch.int32, device=self.device)
-        call('es_dense_index', P(x3.cs.coords), x3.cs.n, x3.cs.ts, X, Y, Z, P(didx), hip.stream())
-        # SparseTensor.dense(): scatter the rows into columns [C2, C2+C3) of the volume buffer
-        call('es_row_move', vol.data_ptr() + 4 * C2, C2 + C3, P(x3.F.d), C3, P(didx), x3.cs.n, C3, 2, hip.stream())
+        x3, didx = self.point_branch(pts, vol, C2, on_backbone=lambda: self.tape_part(2))
         E.mark('point branch (voxelise + MinkResNet + dense)')
         v = E.Var(vol)
 
@@ -147,12 +183,9 @@ class DenseFusionOccPredictor(DetectorBase):
                 acc = 1
                 if f2d.g is None:
                     f2d.g, acc = torch.empty_like(f2d.d), 0         # the gather writes every pixel
-                head = torch.empty(f2d.d.shape[0], dtype=torch.int32, device=self.device)
-                nxt = torch.empty(B * nvox * V, dtype=torch.int32, device=self.device)
-                call('es_point_sample_bwd', P(bidx), B * nvox, V, P(v.g), C2 + C3, P(pix), P(cnt), Hf, Wf, C2, P(f2d.g),
-                     B * V, P(head), P(nxt), acc, hip.stream())
+                project_bwd(v.g, acc)
         E.TAPE.add(bwd)
-        outs = self.neck_3d(v, (X, Y, Z), B, on_coarse=lambda: self.tape_part(3))
+        outs = self.neck_3d(v, (X, Y, Z), n, on_coarse=lambda: self.tape_part(3))
         E.mark('IndoorImVoxelNeck')
         return outs
 

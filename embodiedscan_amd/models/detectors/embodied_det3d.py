@@ -21,6 +21,8 @@ from .sparse_featfusion_single_stage import SparseFeatureFusionSingleStage3DDete
 
 @MODELS.register_module()
 class Embodied3DDetector(SparseFeatureFusionSingleStage3DDetector):
+    continuous = True
+
     predict_chunk = 8
 
     def open_walk(self, metainfo, max_frames=50):

@@ -53,6 +53,8 @@ class _TextFeatMap:
 
 @MODELS.register_module()
 class SparseFeatureFusion3DGrounder(SparseFeatureFusionSingleStage3DDetector):
+    task = 'ground'
+
     def __init__(self, backbone, backbone_3d, bbox_head, neck=None, neck_3d=None, decoder=None, voxel_size=0.01,
                  num_queries=512, max_num_entities=256, coord_type='CAMERA', train_cfg=None, test_cfg=None,
                  data_preprocessor=None, use_xyz_feat=False, init_cfg=None, seed=0, device='cuda:0', text_encoder_cfg=None,

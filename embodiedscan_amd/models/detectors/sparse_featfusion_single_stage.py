@@ -24,6 +24,8 @@ def _stream():
 
 @MODELS.register_module()
 class SparseFeatureFusionSingleStage3DDetector(DetectorBase):
+    task, continuous = 'det3d', False
+
     def __init__(self, backbone, backbone_3d, bbox_head, neck=None, neck_3d=None, coord_type='CAMERA',
                  train_cfg=None, test_cfg=None, data_preprocessor=None, use_xyz_feat=False, init_cfg=None, seed=0,
                  device='cuda:0'):

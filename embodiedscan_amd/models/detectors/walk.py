@@ -26,12 +26,11 @@ counted with no prediction returned -- reset() the walk then."""
 import torch
 from ... import engine as E
 from ... import hip
-from ... import sparse
 from ...hip import P, call
-from ...sparse import SparseTensor
 from ...structures import Det3DDataSample
 from ..layers.fusion_layers.point_fusion import build_fusion_meta
 from .base import predict_guard
+from .dense_fusion_occ import C3
 
 MAX_DET_FRAMES = 64          # es_point_sample_win_fwd returns -9 above that
 
@@ -150,6 +149,10 @@ class _Walk:
         self._frame[0].copy_(img.permute(1, 2, 0))
         return H, W
 
+    def _frame5(self, H, W):
+        """the staged frame as the (1, 1, 3, H, W) block a detector's image branch takes (a view: channels stay innermost)"""
+        return self._frame.view(1, 1, H, W, 3).permute(0, 1, 4, 2, 3)
+
     def _guard(self):
         """eval mode + tape off, both restored on exit"""
         return predict_guard(self.det)
@@ -192,13 +195,11 @@ class OccWalk(_Walk):
             hip.refresh_stream()
             det._bind()
             H, W = self._stage_frame(img)
-            E.refresh_weight_copies()
-            f2d, Hf, Wf = det.neck(det.backbone(self._frame), 1, levels=[0])[0]
+            f2d, Hf, Wf = det.image_maps(self._frame5(H, W))
             meta_dev = self.meta.one_view(depth2img, (H, W)).to(dev, non_blocking=True)
             assert f2d.d.dtype == torch.float32, 'the step kernel reads f32 feature maps (the FPN emits f32)'
-            C2, C3 = int(f2d.d.shape[1]), 512
+            C2 = int(f2d.d.shape[1])
             nvox = self.nvox
-            X, Y, Z = det.n_voxels
             if self.sum is None or self.sum.shape[1] != C2:
                 assert self.t == 0, 'the width of the image volume changed during the walk'
                 self.sum = torch.zeros((nvox, C2), dtype=torch.float32, device=dev)
@@ -211,19 +212,9 @@ class OccWalk(_Walk):
             self.meta.add(depth2img)
             self.cloud.n = n
             self.t += 1
-            # sparse branch on the cloud so far: the calls extract_feat makes for one sample
-            cloud = self.cloud.buf[:n]
-            rmin = det.point_cloud_range[:3]
-            cmax = [k * det.voxel_stride - 1 for k in det.n_voxels]
-            cs, src = sparse.voxelize_range([cloud], rmin, det.voxel_size, cmax)
-            feats = torch.empty((cs.n, 3), dtype=torch.float32, device=dev)
-            call('es_row_move', P(feats), 3, P(cloud), cloud.stride(0), P(src), cs.n, 3, 0, hip.stream())
-            x3 = det.backbone_3d(SparseTensor(cs, E.Var(feats, rg=False)))[-1]
-            assert x3.F.d.shape[1] == C3 and x3.cs.ts == det.voxel_stride
-            didx = torch.empty(x3.cs.n, dtype=torch.int32, device=dev)
-            call('es_dense_index', P(x3.cs.coords), x3.cs.n, x3.cs.ts, X, Y, Z, P(didx), hip.stream())
-            call('es_row_move', vol.data_ptr() + 4 * C2, C2 + C3, P(x3.F.d), C3, P(didx), x3.cs.n, C3, 2, hip.stream())
-            outs = det.neck_3d(E.Var(vol), (X, Y, Z), 1)
+            cloud = self.cloud.buf[:n]                   # the cloud so far, its xyz read in place: no packed copy
+            det.point_branch([cloud], vol, C2, rows=cloud)
+            outs = det.neck_3d(E.Var(vol), tuple(det.n_voxels), 1)
             logits, dims = det.bbox_head.forward(outs[:1])[0]
             self.logits = logits.d
             return det.bbox_head.argmax(logits, dims)[0]
@@ -250,6 +241,26 @@ class _MapWalk(_Walk):
         own = [self.cloud.buf] + [m for m, _, _ in (self.maps or [])]
         return sum(t.numel() * t.element_size() for t in own if t is not None)
 
+    def _refuse_full(self):
+        if self.t >= self.max_frames:
+            raise ValueError(f'the walk was opened for max_frames = {self.max_frames} frames and has seen them all')
+
+    def _intake(self, img, join=False):
+        """the frame through the image branch, its four maps into row block t of the kept ones -> (hw, forked) as _image_feats gives
+        them.  Forked: the copies ride behind the image backbone on its stream; join=True makes whatever the caller queues next see
+        the maps, join=False leaves that to the caller (_fuse_points joins).  Commits nothing: `t` does not move."""
+        H, W = self._stage_frame(img)
+        img_feats, _, hw, forked = self.det._image_feats(self._frame5(H, W))
+        self._alloc_maps(img_feats)                      # (on the main stream: the buffers outlive every side-stream segment)
+        if forked:
+            with E.side_stream(fork=False):
+                self._keep_maps(img_feats)
+            if join:
+                E.join_side()
+        else:
+            self._keep_maps(img_feats)
+        return hw, forked
+
     def _alloc_maps(self, img_feats):
         if self.maps is None or any(m.dtype != f.d.dtype or m.shape[1] != f.d.shape[1] or (h, w) != (Hf, Wf)
                                     for (m, h, w), (f, Hf, Wf) in zip(self.maps, img_feats)):
@@ -273,24 +284,15 @@ class DetWalk(_MapWalk):
 
     def observe(self, img, points, depth2img):
         self._check(img, points)
-        if self.t >= self.max_frames:
-            raise ValueError(f'the walk was opened for max_frames = {self.max_frames} frames and has seen them all')
+        self._refuse_full()
         det = self.det
         t = self.t
         with self._guard():
             hip.refresh_stream()
             det._bind()
-            H, W = self._stage_frame(img)
             self.meta.add(depth2img)
             try:
-                img5 = self._frame.view(1, 1, H, W, 3).permute(0, 1, 4, 2, 3)
-                img_feats, _, hw, forked = det._image_feats(img5)
-                self._alloc_maps(img_feats)              # (on the main stream: the buffers outlive every side-stream segment)
-                if forked:                               # the copies ride behind the image backbone on its stream; _fuse_points joins
-                    with E.side_stream(fork=False):
-                        self._keep_maps(img_feats)
-                else:
-                    self._keep_maps(img_feats)
+                hw, forked = self._intake(img)
                 n = self.cloud.append(points)
                 views = self._views(t + 1)
                 sample = Det3DDataSample(self.meta.metainfo())
@@ -331,24 +333,14 @@ class GroundWalk(_MapWalk):
 
     def observe(self, img, points, depth2img):
         self._check(img, points)
-        if self.t >= self.max_frames:
-            raise ValueError(f'the walk was opened for max_frames = {self.max_frames} frames and has seen them all')
+        self._refuse_full()
         WalkMeta._frame(depth2img)
         det = self.det
         n = self.cloud.append(points)                    # (a cloud with other columns is refused here, before the backbone runs)
         with self._guard():
             hip.refresh_stream()
             det._bind()
-            H, W = self._stage_frame(img)
-            img5 = self._frame.view(1, 1, H, W, 3).permute(0, 1, 4, 2, 3)
-            img_feats, _, hw, forked = det._image_feats(img5)
-            self._alloc_maps(img_feats)                  # (on the main stream: the buffers outlive every side-stream segment)
-            if forked:                                   # the copies ride behind the image backbone on its stream
-                with E.side_stream(fork=False):
-                    self._keep_maps(img_feats)
-                E.join_side()                            # whatever the caller queues next sees the maps
-            else:
-                self._keep_maps(img_feats)
+            hw, _ = self._intake(img, join=True)
         self.meta.add(depth2img)
         self.cloud.n = n
         self._hw = hw

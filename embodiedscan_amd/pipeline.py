@@ -263,6 +263,11 @@ def make_occ_batch(dscans, occ_gts=None):
     return data
 
 
+def projection_key(meta):
+    """the key under which a scan's meta carries its projection entry (a dict of extrinsic / intrinsic / origin)"""
+    return next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(meta.get(k), dict))
+
+
 def prefix_lengths(points_slice_indices, n_rows):
     """rows of the cloud that prefix t = 0 .. T-1 holds.  ConstructMultiSweeps (multiview.py:183-216) concatenates the slices
     [s[0]:s[1]], [s[1]:s[2]], ... of the cloud it is handed; the indices were saved BEFORE PointsRangeFilter thinned that cloud
@@ -276,7 +281,7 @@ def make_cont_occ_batch(dscan, occ=None):
     is the list of the T cumulative clouds ConstructMultiSweeps builds (multiview.py:183-216) -- here T row-prefix VIEWS of the one
     un-projected device buffer (prefix t = its first points_slice_indices[t + 1] rows; no copy) -- and the single data sample
     carries `gt_occupancy` and the list-valued per-prefix `gt_occupancy_masks`; Det3DDataPreprocessor(batchwise_inputs=True)
-    turns it into T samples.  occ None: the scan carries both itself."""
+    turns it into T samples.  occ None: the scan carries both itself; a mask may be None (a recording without ground truth)."""
     sl = dscan['points_slice_indices']
     data = make_batch([dscan])
     pts = data['inputs']['points'][0]
@@ -284,7 +289,7 @@ def make_cont_occ_batch(dscan, occ=None):
     occ = occ if occ is not None else dscan
     ds = data['data_samples'][0]
     ds.gt_occupancy = torch.as_tensor(occ['gt_occupancy'])
-    ds.gt_occupancy_masks = [torch.as_tensor(m) for m in occ['gt_occupancy_masks']]
+    ds.gt_occupancy_masks = [None if m is None else torch.as_tensor(m) for m in occ['gt_occupancy_masks']]
     assert len(ds.gt_occupancy_masks) == len(sl) - 1, 'one visibility mask per prefix'
     return data
 
@@ -324,8 +329,7 @@ def walk_frames(dscan, n_rows=None):
     sl = dscan['points_slice_indices']
     if n_rows is None:
         n_rows = int(dscan['sel_pix'].numel()) if 'sel_pix' in dscan else int(sl[-1])
-    key = next(k for k in ('depth2img', 'lidar2img', 'cam2img') if isinstance(dscan['meta'].get(k), dict))
-    pm = dscan['meta'][key]
+    pm = dscan['meta'][projection_key(dscan['meta'])]
     r0 = 0
     for t, r1 in enumerate(prefix_lengths(sl, n_rows)):
         yield t, (r0, max(r0, r1)), pm['extrinsic'][t], pm['intrinsic'][t]
