@@ -237,6 +237,145 @@ extern "C" int es_box3d_iou_filter(const float* boxes, const float* scores, cons
   return 0;
 }
 
+// ------------------------------------------------------------------ track table: one frame's detections against the tracks
+// Stable identities over a walk (embodiedscan_amd/tracks.py; the reference has no tracker, the definition is include/es_hip.h's).
+// iou (n, ld) is what es_box3d_iou(det_boxes, n, trk_boxes, m) stored: the clipping stays in that all-CU kernel, this one clips
+// nothing.  A pair (j, i) is a candidate when i < min(m, n_tracks), the track is alive, iou[j][i] > iou_thr (f32, a NaN never is)
+// and, with same_class, the labels agree.  The greedy walks the candidates by descending IoU, ties to the lower row, then the lower
+// slot, and takes a pair whose two ends are free.  That order is strict and total, so the greedy equals repeated rounds of MUTUAL
+// BEST pairs: a pair that is the best free candidate of its row and of its column is taken by the greedy before anything that shares
+// an end with it, and taking it changes nothing for the other pairs of the round.  A round is parallel in the pairs: the key
+// iou_bits << 32 | (2047 - j) << 12 | (4095 - i) (positive floats order like their bits) goes into rowbest[j] and colbest[i] by
+// 64-bit LDS atomicMax, a pair is taken iff rowbest[j] == colbest[i] != 0, and the loop ends on a round that takes nothing (the
+// largest key left is always mutual, so nothing is left then).  A free row without a candidate never gets one again (columns only
+// leave) and is not scanned again: after the first round only the contested rows are read.  Then the unmatched rows are numbered in
+// row order by a workgroup prefix sum (births), every row writes its track, and the tracks nobody matched age.
+#define TRK_MAX_DET 2048
+#define TRK_MAX_CAP 4096
+#define TRK_T 1024
+__global__ __launch_bounds__(TRK_T) void k_track_assign(const float* __restrict__ iou, int n, int m, int ld, const float* __restrict__ det_boxes,
+                                                        const float* __restrict__ det_scores, const int* __restrict__ det_labels,
+                                                        float* trk_boxes, float* trk_f, int* trk_i, int* counts, int cap, int t,
+                                                        float iou_thr, int same_class, int max_age, int* __restrict__ det_track) {
+  __shared__ unsigned long long s_rowbest[TRK_MAX_DET];    // 16 KB
+  __shared__ unsigned long long s_colbest[TRK_MAX_CAP];    // 32 KB
+  __shared__ short s_row[TRK_MAX_DET];                     // -1 free, -2 free for good (no candidate left), else the matched slot
+  __shared__ unsigned char s_col[TRK_MAX_CAP];             // 0 not a column (dead), 1 free, 2 taken
+  __shared__ int s_wcnt[TRK_T / 64];
+  __shared__ int s_taken;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt0 = min(max(counts[0], 0), cap);
+  const int mm = min(m, nt0);                              // columns at or above hold whatever the host's bound left there
+  for (int j = tid; j < n; j += TRK_T) s_row[j] = -1;
+  for (int i = tid; i < mm; i += TRK_T) s_col[i] = trk_i[(size_t)i * 5 + 4] != 0 ? 1 : 0;
+  __syncthreads();
+  if (n > 0 && mm > 0) {
+    while (true) {
+      for (int j = tid; j < n; j += TRK_T) s_rowbest[j] = 0ull;
+      for (int i = tid; i < mm; i += TRK_T) s_colbest[i] = 0ull;
+      if (tid == 0) s_taken = 0;
+      __syncthreads();
+      for (int j = w; j < n; j += TRK_T / 64) {            // a wave per free row, its lanes along the columns
+        if (s_row[j] != -1) continue;
+        const float* __restrict__ row = iou + (size_t)j * ld;
+        const int dl = same_class ? det_labels[j] : 0;
+        unsigned long long best = 0ull;
+        for (int i0 = lane; i0 < mm; i0 += 256) {
+          float v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[u] = i0 + 64 * u < mm ? row[i0 + 64 * u] : 0.f;     // (0 is no candidate: iou_thr >= 0)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int i = i0 + 64 * u;
+            if (!(v[u] > iou_thr) || s_col[i] != 1) continue;
+            if (same_class && trk_i[(size_t)i * 5] != dl) continue;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(v[u]) << 32) | ((unsigned long long)(2047 - j) << 12) |
+                                           (unsigned long long)(4095 - i);
+            atomicMax(&s_colbest[i], key);
+            if (key > best) best = key;
+          }
+        }
+        if (best) atomicMax(&s_rowbest[j], best);
+      }
+      __syncthreads();
+      for (int j = tid; j < n; j += TRK_T) {
+        if (s_row[j] != -1) continue;
+        const unsigned long long k = s_rowbest[j];
+        if (!k) { s_row[j] = -2; continue; }
+        const int i = 4095 - (int)(k & 4095ull);
+        if (s_colbest[i] == k) { s_row[j] = (short)i; s_col[i] = 2; s_taken = 1; }
+      }
+      __syncthreads();
+      const int taken = s_taken;
+      __syncthreads();                                     // every lane has read s_taken before the next round clears it
+      if (!taken) break;
+    }
+  }
+  // matched rows update their track; unmatched rows are born in row order into nt0, nt0 + 1, ... while the table has room
+  int born = 0;
+  for (int base = 0; base < n; base += TRK_T) {
+    const int j = base + tid;
+    const int r = j < n ? (int)s_row[j] : 0;
+    const bool un = j < n && r < 0;
+    const unsigned long long bal = __ballot(un);
+    if (lane == 0) s_wcnt[w] = __popcll(bal);
+    __syncthreads();
+    int before = born, total = 0;
+#pragma unroll
+    for (int k = 0; k < TRK_T / 64; ++k) {
+      const int c = s_wcnt[k];
+      if (k < w) before += c;
+      total += c;
+    }
+    __syncthreads();                                       // every lane has read s_wcnt before the next chunk rewrites it
+    born += total;
+    if (j >= n) continue;
+    int slot = r;
+    if (un) {
+      slot = nt0 + before + __popcll(bal & ((1ull << lane) - 1ull));
+      if (slot >= cap) slot = -1;                          // the table is full: the detection is dropped
+    }
+    det_track[j] = slot;
+    if (slot < 0) continue;
+    const float sc = det_scores[j];
+    const int lb = det_labels[j];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) trk_boxes[(size_t)slot * 9 + c] = det_boxes[(size_t)j * 9 + c];
+    trk_f[(size_t)slot * 2] = sc;
+    int* ti = trk_i + (size_t)slot * 5;
+    if (un) {
+      trk_f[(size_t)slot * 2 + 1] = sc;
+      ti[0] = lb; ti[1] = t; ti[2] = t; ti[3] = 1; ti[4] = 1;
+    } else {
+      if (sc >= trk_f[(size_t)slot * 2 + 1]) { trk_f[(size_t)slot * 2 + 1] = sc; ti[0] = lb; }
+      ti[2] = t;
+      ti[3] += 1;
+    }
+  }
+  // ageing, after the births: a track matched or born now has last_seen = t and stays; the others are rows nobody wrote in this launch
+  if (max_age >= 0) {
+    for (int i = tid; i < nt0; i += TRK_T) {
+      if (i < mm && s_col[i] == 2) continue;
+      int* ti = trk_i + (size_t)i * 5;
+      if (ti[4] != 0 && (long long)t - (long long)ti[2] > (long long)max_age) ti[4] = 0;
+    }
+  }
+  if (tid == 0) {
+    const int want = nt0 + born;
+    counts[0] = min(want, cap);
+    if (want > cap) counts[1] += want - cap;
+  }
+}
+extern "C" int es_track_assign(const float* iou, int n, int m, int ld, const float* det_boxes, const float* det_scores, const int* det_labels,
+                               float* trk_boxes, float* trk_f, int* trk_i, int* counts, int cap, int t, float iou_thr, int same_class,
+                               int max_age, int* det_track, void* stream) {
+  if (n < 0 || n > TRK_MAX_DET || cap < 1 || cap > TRK_MAX_CAP || m < 0 || m > cap || ld < m || !(iou_thr >= 0.0f)) return -4;
+  hipLaunchKernelGGL(k_track_assign, dim3(1), dim3(TRK_T), 0, (hipStream_t)stream, iou, n, m, ld, det_boxes, det_scores, det_labels, trk_boxes,
+                     trk_f, trk_i, counts, cap, t, iou_thr, same_class, max_age, det_track);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------ box_iou3d with its two polygons in LDS
 // faces_flux keeps two 16-vertex polygons per lane in scratch (1 KB).  The same routine with the polygons in an LDS column per lane
 // -- vertex i, component c of lane q at [(i * 3 + c) * CLIP_LANES + q], so that a wave's accesses are conflict free -- and the two

@@ -2,6 +2,7 @@
 the model consumed: the reference's demo (demo/demo.py) without the 3-D viewer.
 
     python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json] [--render DIR]
+                                         [--track [--track-iou X] [--track-max-age K]]
 
 reads D/S/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}, runs the model of CONFIG in
 `predict` mode (or frame by frame through a walk session with --walk) and writes the filtered boxes, scores, labels and class names
@@ -16,6 +17,10 @@ compared in f32, like the score, against the f32 value of the threshold; a NaN I
 render=DIR (run_scene, walk_scene, --render): frame_0000.png ... = dscan['img'] -- the resized frames the image backbone saw -- under the
 prediction, projected with that sample's own depth2img matrices (frame_matrices), so the picture shows the projection the fusion used;
 legend.json (class name -> colour) lies next to them.  embodiedscan_amd.render draws on the device; with render=None nothing of it runs.
+
+--track (with --walk, the cont-det3d model; walk_scene(track=dict(...))): a tracks.TrackTable is updated with every frame's filtered list,
+the records gain track_ids -- the same object keeps its id from frame to frame -- and --render colours by track (legend.json: track_<id> ->
+{color, class_name}).  Without it nothing of the table runs and every output is what it was.
 
 Asking in words (a grounding configuration):
 
@@ -361,19 +366,59 @@ def _scene_walk(detector, dscan, batch, max_frames, capped):
     return walk, n_frames, frames()
 
 
-def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None):
+def _track_painter(dir, detector, class_names, dscan, table):
+    """the painter of a tracked walk: a box takes the colour of its track, render.class_palette(257)[1:][id % 256], so two chairs differ
+    and one chair keeps its colour when its arg-max label flickers; legend.json maps track_<id> -> {color, class_name} for every track
+    drawn so far (the class of the track's best detection) and is rewritten after every frame"""
+    names, _ = _class_legend(detector, class_names)
+    pal = RD.class_palette(257)[1:]
+    paint = _painter(dir, [], pal, dscan, detector.device,
+                     lambda frames, E, K, res, pal_dev: RD.render_boxes(frames, E, K, res.bboxes_3d, pal_dev[res.track_ids.remainder(256)].contiguous(),
+                                                                        layout='chw'))
+    legend = {}
+
+    def paint_tracks(res, t=None):
+        paint(res, t)
+        ids = res.track_ids.cpu().tolist()
+        labels = table.i[res.track_ids.clamp(min=0), 0].cpu().tolist()
+        for i, l in zip(ids, labels):
+            if i >= 0:
+                legend[f'track_{i}'] = dict(color=[int(c) for c in pal[i % 256]], class_name=names[l] if 0 <= l < len(names) else f'class_{l}')
+        with open(os.path.join(dir, 'legend.json'), 'w') as f:
+            json.dump(legend, f)
+    return paint_tracks
+
+
+def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None, track=None):
     """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene): opens a walk
     session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy).  render: a directory that receives
-    frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn."""
+    frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn.
+    track (cont-det3d): keyword arguments of tracks.TrackTable (dict(): its defaults).  The table is updated with the filtered list of
+    every frame, and the yielded InstanceData gain track_ids (int64; -1: the table was full), track_hits and track_first_seen, all on the
+    device; with render the boxes take their track's colour (_track_painter).  None: no table, nothing of it runs."""
     kind = _kind(detector)
     if kind not in ('cont-det3d', 'cont-occ'):
         raise ValueError(f'{type(detector).__name__} has no walk session: use run_scene')
+    if track is not None and kind != 'cont-det3d':
+        raise ValueError(f'{type(detector).__name__} yields no object list: track= goes with the cont-det3d detector')
     dscan = load_scene(detector, scene_dir, pipeline, seed)
     walk, _, frames = _scene_walk(detector, dscan, make_scene_batch(detector, dscan), max_frames, capped=kind == 'cont-det3d')
-    paint = None if render is None else _prediction_painter(render, detector, class_names, dscan)
+    table = None
+    if track is not None:
+        from .tracks import TrackTable
+        table = TrackTable(detector.device, **track)
+    if render is None:
+        paint = None
+    elif table is None:
+        paint = _prediction_painter(render, detector, class_names, dscan)
+    else:
+        paint = _track_painter(render, detector, class_names, dscan, table)
     for t, frame in frames:
         res = walk.observe(*frame)
         res = res if kind == 'cont-occ' else _filtered(detector, res, filter)
+        if table is not None:
+            res.track_ids = table.update(res, t)
+            res.track_hits, res.track_first_seen = table.lookup(res.track_ids)
         if paint is not None:
             paint(res, t)
         yield t, res
@@ -521,6 +566,9 @@ def main(argv=None):
     ap.add_argument('--topk', type=int, default=1, help='answers per prompt (grounding models)')
     ap.add_argument('--out', default=None, help='JSON file (default: standard output)')
     ap.add_argument('--render', default=None, metavar='DIR', help='write every frame under its prediction as DIR/frame_0000.png ... and DIR/legend.json')
+    ap.add_argument('--track', action='store_true', help='with --walk on a cont-det3d configuration: stable object identities over the walk (track_ids)')
+    ap.add_argument('--track-iou', type=float, default=None, metavar='X', help='a detection continues a track above this IoU (default: 0.25)')
+    ap.add_argument('--track-max-age', type=int, default=None, metavar='K', help='a track unmatched for more than K frames dies (default: never)')
     a = ap.parse_args(argv)
     prompts = list(a.prompt)
     if a.prompts_file is not None:
@@ -535,6 +583,12 @@ def main(argv=None):
         ap.error(f"{cfg['model']['type']} grounds prompts: give --prompt TEXT (repeatable) or --prompts-file F")
     if prompts and not grounder:
         ap.error(f"{cfg['model']['type']} takes no prompt: --prompt / --prompts-file go with a grounding configuration")
+    tracked = a.track or a.track_iou is not None or a.track_max_age is not None
+    if tracked:                                                          # (refused before the model is built as well)
+        cls = MODELS.get(cfg['model']['type'])
+        if not (a.track and a.walk and getattr(cls, 'task', None) == 'det3d' and getattr(cls, 'continuous', False)):
+            ap.error('--track [--track-iou X] [--track-max-age K] follows the objects of a walk: it goes with --walk on a cont-det3d '
+                     f"configuration (got {cfg['model']['type']}{', --walk' if a.walk else ', no --walk'}{'' if a.track else ', no --track'})")
     det, cfg = init_model(cfg, a.checkpoint, a.device)
     scene_dir = os.path.join(a.root_dir, a.scene)
     pipe = pipeline_of(cfg)
@@ -551,6 +605,11 @@ def main(argv=None):
     kind = _kind(det)
     nc = getattr(det.bbox_head, 'num_classes', 0)
     names = _class_names(cfg, nc) if kind in ('det3d', 'cont-det3d') else ['empty'] + _class_names(cfg, max(nc - 1, 0))
+    if a.walk and tracked:
+        trk = dict(({} if a.track_iou is None else dict(iou_thr=a.track_iou)), **({} if a.track_max_age is None else dict(max_age=a.track_max_age)))
+        results = [_record(r, names, t=t, track_ids=r.track_ids.cpu().tolist())
+                   for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, track=trk)]
+        return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=True, filter=flt, track=trk, results=results))
     if a.walk:
         results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names)]
     else:

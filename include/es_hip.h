@@ -606,6 +606,30 @@ int es_box3d_iou(const float* boxes1, int N, const float* boxes2, int M, float* 
  * -4, nothing written: n > 16384 (es_topk_sorted's limit), n_classes outside 1 .. 4096, topk_per_class < 1; -5: n < 0. */
 int es_box3d_iou_filter(const float* boxes, const float* scores, const int* labels, const int* order, int n, int n_classes,
                         float iou_thr, float score_thr, int topk_per_class, int* keep_idx, int* keep_cnt, void* stream);
+/* Object tracks over a walk (embodiedscan_amd/tracks.py; the reference has no tracker: this is the definition).  A track
+ * table of capacity cap: trk_boxes (cap,9), trk_f (cap,2) = score, label_score, trk_i (cap,5) = label, first_seen, last_seen, hits,
+ * alive, counts (2) = n_tracks, dropped.  A slot is an identity and is never reused.  One launch associates the n detections of
+ * frame t (det_boxes (n,9), det_scores (n), det_labels (n) int32) with the table, given iou (n, ld), ld >= m: the [j][i] element
+ * es_box3d_iou(det_boxes, n, trk_boxes, m) stores (the detection first; f64 polyhedral rounded to f32; every comparison is f32).
+ * m is the host's UPPER BOUND on n_tracks: the columns below min(m, counts[0]) are used, the others ignored whatever they hold, so
+ * the caller needs no read-back between frames.
+ *  1. (j, i) is a candidate iff i < n_tracks, track i is alive, iou[j][i] > iou_thr (strict; a NaN never is) and, with same_class,
+ *     det_labels[j] == label[i].
+ *  2. Greedy matching: candidates by descending IoU, ties to the lower row j, then the lower slot i; a pair is taken when both ends
+ *     are free (a strict total order: the result is unique; the kernel finds it in rounds of mutual-best pairs, parallel in the pairs).
+ *  3. Matched (j, i): box and score become the detection's; if det_score >= label_score, label and label_score become the
+ *     detection's; hits += 1; last_seen = t; det_track[j] = i.
+ *  4. Unmatched detections are born in ascending row order into slots n_tracks, n_tracks + 1, ...: first_seen = last_seen = t,
+ *     hits = 1, alive = 1, label_score = score.  A birth that finds the table full: det_track[j] = -1, dropped += 1.
+ *  5. Ageing, after the births: an alive track with t - last_seen > max_age dies (max_age < 0: never); it keeps its row and its id
+ *     and is never matched again.
+ * det_track (n) is written, nothing behind it; slots at or above the new n_tracks stay untouched.  n = 0 still launches and ages.
+ * One workgroup, 56 KB of static LDS, no scratch.
+ * -4, nothing written, nothing launched: n outside 0 .. 2048, cap outside 1 .. 4096, m < 0, m > cap, ld < m, iou_thr negative or NaN. */
+int es_track_assign(const float* iou, int n, int m, int ld, const float* det_boxes, const float* det_scores, const int* det_labels,
+                    float* trk_boxes /*(cap,9)*/, float* trk_f /*(cap,2): score, label_score*/,
+                    int* trk_i /*(cap,5): label, first_seen, last_seen, hits, alive*/, int* counts /*(2): n_tracks, dropped*/, int cap,
+                    int t, float iou_thr, int same_class, int max_age, int* det_track /*(n)*/, void* stream);
 /* The answers of a grounder, all prompts in ONE launch (grid = P, one workgroup per prompt; no sorted order is passed in):
  * boxes (P,Q,9), scores (P,Q).  Per prompt, independently, the greedy of es_box3d_iou_filter with one class: rows by descending
  * score (ties to the lower row, -0.0 ties with +0.0); a row with score < score_thr (f32) or a NaN score is never an answer; a row
