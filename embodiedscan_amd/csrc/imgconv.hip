@@ -393,7 +393,10 @@ __global__ __launch_bounds__(256) void k_img_dgrad3_s2(const float* __restrict__
 }
 
 #define ES_S2_LD 48                                         // bf16 elements per padded LDS row (96 B, as HLD of spconv.hip)
-template <int NT>
+template <bool GH, int NB> struct S2Regs { float4 a[4]; uint4 b[NB]; };              // one thread's piece of a chunk: 16 f32 ...
+template <int NB> struct S2Regs<true, NB> { uint4 a[2]; uint4 b[NB]; };             // ... or 16 bf16 gradient channels, and the weights
+// GH: G holds bf16 rows (the pre-rounded values of the same gradient matrix, ldg in elements): staged as they are, same chunks and sums
+template <int NT, bool GH = false>
 __global__ __launch_bounds__(256) void k_img_dgrad1_s2(const float* __restrict__ G, int ldg, const unsigned short* __restrict__ Wn, int n_g,
                                                        int Kred, int Wo, float* __restrict__ dX, int ldx, int accumulate) {
   constexpr int NF = NT / 16;
@@ -429,19 +432,32 @@ __global__ __launch_bounds__(256) void k_img_dgrad1_s2(const float* __restrict__
   const int b_w = ((NT % 64 == 0) || b_n < NT) ? b_n : 0;    // (NT = 32: the upper threads re-read column 0 and store nothing)
   const bool a_ok = row0 + a_r < n_g;
   const float* a_src = G + (size_t)(a_ok ? row0 + a_r : 0) * ldg + a_kk;
-  struct Regs { float4 a[4]; uint4 b[NB]; };
+  const unsigned short* a_srch = (const unsigned short*)G + (size_t)(a_ok ? row0 + a_r : 0) * ldg + a_kk;
+  using Regs = S2Regs<GH, NB>;
   auto load_chunk = [&](Regs& R, int c) {
-    const float4* pa = (const float4*)(a_src + c * 32);
+    if constexpr (GH) {
+      const uint4* ph = (const uint4*)(a_srch + c * 32);
+      R.a[0] = ph[0];
+      R.a[1] = ph[1];
+    } else {
+      const float4* pa = (const float4*)(a_src + c * 32);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) R.a[q] = pa[q];
+      for (int q = 0; q < 4; ++q) R.a[q] = pa[q];
+    }
 #pragma unroll
     for (int h = 0; h < NB; ++h) R.b[h] = *(const uint4*)(Wn + (size_t)(n0 + b_w + h * 64) * Kred + c * 32 + b_kk);
   };
   auto store_chunk = [&](const Regs& R, int buf) {
-    uint4 v0 = make_uint4(es_pack_bf16(R.a[0].x, R.a[0].y), es_pack_bf16(R.a[0].z, R.a[0].w), es_pack_bf16(R.a[1].x, R.a[1].y),
-                          es_pack_bf16(R.a[1].z, R.a[1].w));
-    uint4 v1 = make_uint4(es_pack_bf16(R.a[2].x, R.a[2].y), es_pack_bf16(R.a[2].z, R.a[2].w), es_pack_bf16(R.a[3].x, R.a[3].y),
-                          es_pack_bf16(R.a[3].z, R.a[3].w));
+    uint4 v0, v1;
+    if constexpr (GH) {
+      v0 = R.a[0];
+      v1 = R.a[1];
+    } else {
+      v0 = make_uint4(es_pack_bf16(R.a[0].x, R.a[0].y), es_pack_bf16(R.a[0].z, R.a[0].w), es_pack_bf16(R.a[1].x, R.a[1].y),
+                      es_pack_bf16(R.a[1].z, R.a[1].w));
+      v1 = make_uint4(es_pack_bf16(R.a[2].x, R.a[2].y), es_pack_bf16(R.a[2].z, R.a[2].w), es_pack_bf16(R.a[3].x, R.a[3].y),
+                      es_pack_bf16(R.a[3].z, R.a[3].w));
+    }
     if (!a_ok) v0 = v1 = make_uint4(0u, 0u, 0u, 0u);
     uint4* pa = (uint4*)&As[buf * 128 * LD + a_r * LD + a_kk];
     pa[0] = v0;
@@ -551,15 +567,22 @@ extern "C" int es_img_dgrad1_s2_supported(int n_img, int H, int W, int Cg, int C
 
 extern "C" int es_img_dgrad1_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int Cg, int Cx, float* dX, int ldx,
                                      int accumulate, void* stream) {
+  const bool gh = (accumulate & 2) != 0;       // bit 1: G holds bf16 rows, the pre-rounded values of the f32 matrix (ldg in elements)
+  accumulate &= 1;
   if (!img_dgrad1_s2_check(n_img, H, W, Cg, Cx, G, ldg, Wn_bf16, dX, ldx)) return -4;
-  if (G == nullptr || Wn_bf16 == nullptr || dX == nullptr) return -4;
+  if (G == nullptr || Wn_bf16 == nullptr || dX == nullptr || (gh && (ldg % 8))) return -4;
   hipStream_t st = (hipStream_t)stream;
   const unsigned short* Wn = (const unsigned short*)Wn_bf16;
   const int n_g = n_img * (H / 2) * (W / 2), Wo = W / 2;
-  if (Cx % 128 == 0)
-    hipLaunchKernelGGL((k_img_dgrad1_s2<128>), dim3(es_cdiv(n_g, 128), Cx / 128), dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+  const dim3 g128(es_cdiv(n_g, 128), Cx / 128), g32(es_cdiv(n_g, 128), Cx / 32);
+  if (Cx % 128 == 0 && gh)
+    hipLaunchKernelGGL((k_img_dgrad1_s2<128, true>), g128, dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+  else if (Cx % 128 == 0)
+    hipLaunchKernelGGL((k_img_dgrad1_s2<128>), g128, dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+  else if (gh)
+    hipLaunchKernelGGL((k_img_dgrad1_s2<32, true>), g32, dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
   else
-    hipLaunchKernelGGL((k_img_dgrad1_s2<32>), dim3(es_cdiv(n_g, 128), Cx / 32), dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
+    hipLaunchKernelGGL((k_img_dgrad1_s2<32>), g32, dim3(256), 0, st, G, ldg, Wn, n_g, Cg, Wo, dX, ldx, accumulate);
   ES_CHECK_LAUNCH();
   return 0;
 }

@@ -196,7 +196,8 @@ extern "C" int es_img_wgrad_set_option(int key, int value) {
 // is nothing to gather: a workgroup streams a slice of rows in 64-row steps -- X tile [64][CI] by LDS-DMA, dY tile [64][CO] f32 through
 // registers (prefetched one step ahead, rounded to bf16) -- into two LDS buffers and reads both operands transposed; a (CI x CO) tile of dW
 // per workgroup (128 x 128 at most: 16 accumulator fragments per wave), partial tensors per slice added in slice order.
-template <int CI, int CO>
+// YH: dY holds bf16 rows (the pre-rounded values of the same matrix, ldy in elements): loaded as they are, same steps and sums.
+template <int CI, int CO, bool YH = false>
 __global__ __launch_bounds__(256) void k_rows_wgrad1(const unsigned short* __restrict__ Xh, int ldx, const float* __restrict__ dY, int ldy,
                                                      int n, int Cin, int Cout, int rows_per_slice, float* __restrict__ out, int to_ws,
                                                      int accumulate) {
@@ -227,12 +228,16 @@ __global__ __launch_bounds__(256) void k_rows_wgrad1(const unsigned short* __res
                                        (__attribute__((address_space(3))) void*)(smem + buf * XT + (j * 4 + wv) * 1024), 16, 0, 0);
     }
   };
-  float4 yreg[NLY];
+  float4 yreg[YH ? 1 : NLY];
+  uint2 yregh[YH ? NLY : 1];
   auto load_y = [&](int row) {
 #pragma unroll
     for (int j = 0; j < NLY; ++j) {
       const int e = j * 256 + t, rr = e / (CO / 4), c4 = e - rr * (CO / 4);
-      yreg[j] = row + rr < r1 ? *(const float4*)(dY + (size_t)(row + rr) * ldy + n0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (YH)
+        yregh[j] = row + rr < r1 ? *(const uint2*)((const unsigned short*)dY + (size_t)(row + rr) * ldy + n0 + c4 * 4) : make_uint2(0u, 0u);
+      else
+        yreg[j] = row + rr < r1 ? *(const float4*)(dY + (size_t)(row + rr) * ldy + n0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
   auto store_y = [&](int buf) {
@@ -240,8 +245,12 @@ __global__ __launch_bounds__(256) void k_rows_wgrad1(const unsigned short* __res
     for (int j = 0; j < NLY; ++j) {
       const int e = j * 256 + t, rr = e / (CO / 4), c4 = e - rr * (CO / 4);
       uint2 v;
-      v.x = es_pack_bf16(yreg[j].x, yreg[j].y);
-      v.y = es_pack_bf16(yreg[j].z, yreg[j].w);
+      if (YH) {
+        v = yregh[j];
+      } else {
+        v.x = es_pack_bf16(yreg[j].x, yreg[j].y);
+        v.y = es_pack_bf16(yreg[j].z, yreg[j].w);
+      }
       *(uint2*)(smem + 2 * XT + buf * YT + rr * RBY + c4 * 8) = v;
     }
   };
@@ -338,6 +347,8 @@ extern "C" size_t es_rows_wgrad1_workspace_floats(int n, int Cin, int Cout) {
 extern "C" int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n, int Cin, int Cout, float* dW, int accumulate,
                                    float* ws, size_t ws_floats, void* stream) {
   int ci, co, slices, rows;
+  const bool yh = (accumulate & 2) != 0;      // bit 1: dY holds bf16 rows, the pre-rounded values of the f32 matrix (ldy in elements)
+  accumulate &= 1;
   if (!rows_wgrad_check(n, Cin, Cout, Xh, ldx, dY, ldy, ci, co, slices, rows)) return -4;
   if (slices > 1 && (ws == nullptr || ws_floats < (size_t)slices * Cin * Cout)) return -5;
   hipStream_t st = (hipStream_t)stream;
@@ -345,7 +356,11 @@ extern "C" int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int
   float* out = slices > 1 ? ws : dW;
   const int to_ws = slices > 1;
   dim3 grid(slices, Cin / ci, Cout / co);
-#define RW_LAUNCH(CI_, CO_) hipLaunchKernelGGL((k_rows_wgrad1<CI_, CO_>), grid, dim3(256), 0, st, X, ldx, dY, ldy, n, Cin, Cout, rows, out, to_ws, accumulate)
+#define RW_LAUNCH(CI_, CO_)                                                                                                              \
+  do {                                                                                                                                   \
+    if (yh) hipLaunchKernelGGL((k_rows_wgrad1<CI_, CO_, true>), grid, dim3(256), 0, st, X, ldx, dY, ldy, n, Cin, Cout, rows, out, to_ws, accumulate); \
+    else hipLaunchKernelGGL((k_rows_wgrad1<CI_, CO_>), grid, dim3(256), 0, st, X, ldx, dY, ldy, n, Cin, Cout, rows, out, to_ws, accumulate);           \
+  } while (0)
   if (ci == 128 && co == 320) RW_LAUNCH(128, 320);
   else if (ci == 128 && co == 128) RW_LAUNCH(128, 128);
   else if (ci == 128 && co == 64) RW_LAUNCH(128, 64);

@@ -484,7 +484,8 @@ __global__ __launch_bounds__(FCH * FST) void k_norm_bwd_finalize(const float* __
 __global__ void k_norm_bwd_apply(const float* __restrict__ dz, int ldd, const float* __restrict__ x, int ldx, int n,
                                  int C, Segs segs, const float* __restrict__ mean, const float* __restrict__ invstd,
                                  const float* __restrict__ w, const float* __restrict__ sum_dz,
-                                 const float* __restrict__ sum_dzx, float* __restrict__ dx, int ldo, int accumulate) {
+                                 const float* __restrict__ sum_dzx, float* __restrict__ dx, int ldo, int accumulate,
+                                 unsigned short* __restrict__ dxh) {
   size_t tot = (size_t)n * C;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
     int r = (int)(e / C), c = (int)(e - (size_t)r * C);
@@ -493,8 +494,12 @@ __global__ void k_norm_bwd_apply(const float* __restrict__ dz, int ldd, const fl
     float is = invstd[sg * C + c];
     float xh = (x[(size_t)r * ldx + c] - mean[sg * C + c]) * is;
     float g = w[c] * is * (dz[(size_t)r * ldd + c] - sum_dz[sg * C + c] * inv_n - xh * sum_dzx[sg * C + c] * inv_n);
-    float* p = dx + (size_t)r * ldo + c;
-    *p = accumulate ? (*p + g) : g;
+    if (dx) {
+      float* p = dx + (size_t)r * ldo + c;
+      *p = accumulate ? (*p + g) : g;
+    } else {                                                     // no f32 rows asked for: the bf16 rows alone (es_norm_bwd)
+      dxh[(size_t)r * C + c] = (unsigned short)es_pack_bf16(g, 0.f);
+    }
   }
 }
 __global__ __launch_bounds__(256) void k_norm_bwd_apply4(const float* __restrict__ dz, int ldd,
@@ -514,7 +519,7 @@ __global__ __launch_bounds__(256) void k_norm_bwd_apply4(const float* __restrict
     float4 x0 = *(const float4*)(x + (size_t)r0 * ldx + c0), x1 = *(const float4*)(x + (size_t)r1 * ldx + c1);
     float4 g0 = *(const float4*)(dz + (size_t)r0 * ldd + c0), g1 = *(const float4*)(dz + (size_t)r1 * ldd + c1);
     float4 o0 = make_float4(0, 0, 0, 0), o1 = o0;
-    if (accumulate) { o0 = *(const float4*)(dx + (size_t)r0 * ldo + c0); o1 = *(const float4*)(dx + (size_t)r1 * ldo + c1); }
+    if (accumulate && dx) { o0 = *(const float4*)(dx + (size_t)r0 * ldo + c0); o1 = *(const float4*)(dx + (size_t)r1 * ldo + c1); }
 #define NB_ELT(xe, ge, oe, me, ie, we, se, qe) \
     { float xh = ((xe) - (me)) * (ie); float gg = (we) * (ie) * ((ge) - (se) * inv_n - xh * (qe) * inv_n); oe = accumulate ? ((oe) + gg) : gg; }
 #define NB_ONE(xv, gv, ov, r, c)                                                                               \
@@ -526,7 +531,7 @@ __global__ __launch_bounds__(256) void k_norm_bwd_apply4(const float* __restrict
       float4 sq = *(const float4*)(sum_dzx + sg * C + c);                                                      \
       NB_ELT(xv.x, gv.x, ov.x, m.x, is.x, ww.x, sd.x, sq.x) NB_ELT(xv.y, gv.y, ov.y, m.y, is.y, ww.y, sd.y, sq.y) \
       NB_ELT(xv.z, gv.z, ov.z, m.z, is.z, ww.z, sd.z, sq.z) NB_ELT(xv.w, gv.w, ov.w, m.w, is.w, ww.w, sd.w, sq.w) \
-      *(float4*)(dx + (size_t)r * ldo + c) = ov;                                                               \
+      if (dx) *(float4*)(dx + (size_t)r * ldo + c) = ov;                                                       \
       if (dxh) *(uint2*)(dxh + (size_t)r * C + c) = make_uint2(es_pack_bf16(ov.x, ov.y), es_pack_bf16(ov.z, ov.w)); \
     }
     NB_ONE(x0, g0, o0, r0, c0)
@@ -602,7 +607,7 @@ __global__ __launch_bounds__(512) void k_norm_bwd_cb(float* __restrict__ dy, int
       int rc = r < n ? r : rb;
       g[u] = *(const float4*)(dy + (size_t)rc * ldd + c);                       // dz: written above by this very thread
       xv[u] = *(const float4*)(x + (size_t)rc * ldx + c);
-      ov[u] = accumulate ? *(const float4*)(dx + (size_t)rc * ldo + c) : make_float4(0, 0, 0, 0);
+      ov[u] = (accumulate && dx) ? *(const float4*)(dx + (size_t)rc * ldo + c) : make_float4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -613,7 +618,7 @@ __global__ __launch_bounds__(512) void k_norm_bwd_cb(float* __restrict__ dy, int
       NCB_ELT(xv[u].x, g[u].x, ov[u].x, m.x, is.x, ww.x, sd[0], sq[0]) NCB_ELT(xv[u].y, g[u].y, ov[u].y, m.y, is.y, ww.y, sd[1], sq[1])
       NCB_ELT(xv[u].z, g[u].z, ov[u].z, m.z, is.z, ww.z, sd[2], sq[2]) NCB_ELT(xv[u].w, g[u].w, ov[u].w, m.w, is.w, ww.w, sd[3], sq[3])
 #undef NCB_ELT
-      *(float4*)(dx + (size_t)r * ldo + c) = ov[u];
+      if (dx) *(float4*)(dx + (size_t)r * ldo + c) = ov[u];
       if (dxh) *(uint2*)(dxh + (size_t)r * C + c) = make_uint2(es_pack_bf16(ov[u].x, ov[u].y), es_pack_bf16(ov[u].z, ov[u].w));
     }
   }
@@ -626,6 +631,9 @@ extern "C" int es_norm_bwd(float* dy, int ldd, const float* y, int ldy, const fl
                            int ldo, int accumulate, void* dx_bf16, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (n <= 0 || nseg > ES_MAX_SEG) return nseg > ES_MAX_SEG ? -3 : 0;
+  // dx == NULL: the bf16 rows are the only copy of the gradient (its readers all take dx_bf16): no f32 store, nothing to accumulate onto
+  if (!dx && (!dx_bf16 || accumulate)) return -2;
+  if (!dx) ldo = C;
   Segs s = make_segs(seg_off, nseg);
   const int NCH = norm_chunk_rows(max_seg_rows(s));
   int nchunk = es_cdiv(max_seg_rows(s), NCH);
@@ -658,8 +666,8 @@ extern "C" int es_norm_bwd(float* dy, int ldd, const float* y, int ldy, const fl
     int g = es_cdiv((long long)n * C, 256);
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(k_norm_bwd_apply, dim3(g), dim3(256), 0, st, dy, ldd, x, ldx, n, C, s, mean, invstd, weight,
-                       sums, sums + (size_t)nseg * C, dx, ldo, accumulate);
-    if (dx_bf16) return es_cast_rows_bf16(dx, ldo, n, C, dx_bf16, stream);
+                       sums, sums + (size_t)nseg * C, dx, ldo, accumulate, (unsigned short*)dx_bf16);
+    if (dx && dx_bf16) return es_cast_rows_bf16(dx, ldo, n, C, dx_bf16, stream);
   }
   ES_CHECK_LAUNCH();
   return 0;
@@ -1238,6 +1246,74 @@ extern "C" int es_affine_act_bwd_yh(const float* dy, const void* y_bf16, const f
   int g = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
   hipLaunchKernelGGL(k_affine_act_bwd4_yh, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (const uint2*)y_bf16,
                      (const float4*)scale, n4, C / 4, act, (float4*)dx, acc_x, (float4*)dres, acc_r);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+// k_affine_act_bwd4_yh with dx written as bf16 rows (es_pack_bf16 of the f32 value it would store): the gradient of a convolution
+// output whose readers -- that layer's data- and weight-gradient launches -- round it to bf16 on load anyway.  dres stays f32.
+__global__ void k_affine_act_bwd4_yh_xh(const float4* __restrict__ dy, const uint2* __restrict__ y,
+                                        const float4* __restrict__ scale, size_t n4, int C4, int act,
+                                        uint2* __restrict__ dxh, float4* __restrict__ dres, int acc_r) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
+    float4 g = dy[e];
+    if (act) {
+      uint2 v = y[e];
+      if (!(__uint_as_float(v.x << 16) > 0.f)) g.x = 0.f;
+      if (!(__uint_as_float(v.x & 0xffff0000u) > 0.f)) g.y = 0.f;
+      if (!(__uint_as_float(v.y << 16) > 0.f)) g.z = 0.f;
+      if (!(__uint_as_float(v.y & 0xffff0000u) > 0.f)) g.w = 0.f;
+    }
+    float4 s = scale[e % C4];
+    dxh[e] = make_uint2(es_pack_bf16(g.x * s.x, g.y * s.y), es_pack_bf16(g.z * s.z, g.w * s.w));
+    if (dres) {
+      float4 o = g;
+      if (acc_r) { float4 p = dres[e]; o.x = p.x + g.x; o.y = p.y + g.y; o.z = p.z + g.z; o.w = p.w + g.w; }
+      dres[e] = o;
+    }
+  }
+}
+// the join of a downsample block: two bf16 matrices (dz * scale for conv3, dz * scale2 for the downsample convolution), no dres
+__global__ void k_affine_act_bwd4_yh_xh2(const float4* __restrict__ dy, const uint2* __restrict__ y, const float4* __restrict__ scale,
+                                         const float4* __restrict__ scale2, size_t n4, int C4, int act, uint2* __restrict__ dxh,
+                                         uint2* __restrict__ dxh2) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
+    float4 g = dy[e];
+    if (act) {
+      uint2 v = y[e];
+      if (!(__uint_as_float(v.x << 16) > 0.f)) g.x = 0.f;
+      if (!(__uint_as_float(v.x & 0xffff0000u) > 0.f)) g.y = 0.f;
+      if (!(__uint_as_float(v.y << 16) > 0.f)) g.z = 0.f;
+      if (!(__uint_as_float(v.y & 0xffff0000u) > 0.f)) g.w = 0.f;
+    }
+    float4 s = scale[e % C4], s2 = scale2[e % C4];
+    dxh[e] = make_uint2(es_pack_bf16(g.x * s.x, g.y * s.y), es_pack_bf16(g.z * s.z, g.w * s.w));
+    dxh2[e] = make_uint2(es_pack_bf16(g.x * s2.x, g.y * s2.y), es_pack_bf16(g.z * s2.z, g.w * s2.w));
+  }
+}
+extern "C" int es_affine_act_bwd_yh_xh2(const float* dy, const void* y_bf16, const float* scale, const float* scale2, size_t n, int C,
+                                        int act, void* dx_bf16, void* dx2_bf16, void* stream) {
+  if (act == 2 || !dx_bf16 || !dx2_bf16 || !scale2) return -2;
+  if (n == 0) return 0;
+  if ((C % 4) || ((((uintptr_t)dy) | ((uintptr_t)scale) | ((uintptr_t)scale2)) & 15) ||
+      ((((uintptr_t)y_bf16) | ((uintptr_t)dx_bf16) | ((uintptr_t)dx2_bf16)) & 7))
+    return -7;
+  size_t n4 = n * (size_t)(C / 4);
+  int g = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+  hipLaunchKernelGGL(k_affine_act_bwd4_yh_xh2, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (const uint2*)y_bf16,
+                     (const float4*)scale, (const float4*)scale2, n4, C / 4, act, (uint2*)dx_bf16, (uint2*)dx2_bf16);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_affine_act_bwd_yh_xh(const float* dy, const void* y_bf16, const float* scale, size_t n, int C, int act,
+                                       void* dx_bf16, float* dres, int acc_r, void* stream) {
+  if (act == 2 || !dx_bf16) return -2;
+  if (n == 0) return 0;
+  if ((C % 4) || ((((uintptr_t)dy) | ((uintptr_t)scale) | ((uintptr_t)dres)) & 15) || ((((uintptr_t)y_bf16) | ((uintptr_t)dx_bf16)) & 7))
+    return -7;
+  size_t n4 = n * (size_t)(C / 4);
+  int g = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+  hipLaunchKernelGGL(k_affine_act_bwd4_yh_xh, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (const uint2*)y_bf16,
+                     (const float4*)scale, n4, C / 4, act, (uint2*)dx_bf16, (float4*)dres, acc_r);
   ES_CHECK_LAUNCH();
   return 0;
 }

@@ -2904,11 +2904,17 @@ static WgradPlan wgrad_plan_bf16(int XH, int YH, const void* X, int ldx, const v
   return WgradPlan{1, es_cdiv(n_out, rows_per_split), rows_per_split};
 }
 
-template <int XH, int YH>
+// PRE (with YH): dY holds the PRE-ROUNDED rows of an f32 gradient matrix that was never stored (dy_half = 3) -- the plan, the tile and the
+// kernel family are those of the f32-rows form on that matrix (same leading dimension), so the result is that form's, bit for bit.
+// The -4 refusals below are final for such a caller -- the f32 matrix does not exist, there is nothing to fall back to: whoever writes the
+// bf16 rows checks first that its shapes cannot meet them (engine._pre16_ok: bf16 X rows, Cout % 8, fresh contiguous rows)
+template <int XH, int YH, bool PRE = false>
 static int wgrad_bf16_launch(const void* X, int ldx, const void* dY, int ldy, const int* nbr, int n_out, int n_in, int K,
                              int Cin, int Cout, float* dW, int accumulate, float* ws, size_t ws_floats, void* stream) {
   if (n_out <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  const WgradPlan p = wgrad_plan_bf16(XH, YH, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, ws != nullptr);
+  if (PRE && ((ldy % 8) || (((uintptr_t)dY) & 15))) return -4;         // (what the 16-byte bf16 loads of the large tile ask for)
+  const WgradPlan p = wgrad_plan_bf16(XH, PRE ? 0 : YH, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, ws != nullptr);
+  if (PRE && p.kind == 5) return -4;                                   // (the small-linear tile reads f32 rows)
   const size_t nw = (size_t)K * Cin * Cout;
   if (p.splits > 1 && ws_floats < (size_t)p.splits * nw) return -5;
   float* wsk = p.splits > 1 ? ws : nullptr;
@@ -2921,7 +2927,7 @@ static int wgrad_bf16_launch(const void* X, int ldx, const void* dY, int ldy, co
     dim3 grid(K * (Cin / 256), Cout / 256, gz);
     hipLaunchKernelGGL(k_spconv_wgrad_bf16_huge, grid, dim3(512), 0, st, (const unsigned short*)X, ldx,
                        (const unsigned short*)dY, ldy, nbr, n_out, n_in, K, Cin, Cout, p.rows_per_split, p.splits, dW, wsk, accumulate);
-  } else if (p.kind == 2 && XH && YH && ES_OPT_WGRAD_TR && (ldx % 8 == 0) && (ldy % 8 == 0)) {
+  } else if (p.kind == 2 && XH && YH && !PRE && ES_OPT_WGRAD_TR && (ldx % 8 == 0) && (ldy % 8 == 0)) {
     dim3 grid(K * (Cin / 128), Cout / 128, gz);                // experimental: LDS-DMA staging + transposed LDS reads
     if (ES_OPT_WGRAD_TR == 2)
       hipLaunchKernelGGL(k_spconv_wgrad_bf16_tr<64>, grid, dim3(256), 0, st, (const unsigned short*)X, ldx, (const unsigned short*)dY,
@@ -2951,6 +2957,10 @@ extern "C" int es_spconv_wgrad_bf16(const float* X, int ldx, const float* dY, in
 extern "C" int es_spconv_wgrad_bf16_src(const void* X, int x_half, int ldx, const void* dY, int dy_half, int ldy,
                                         const int* nbr, int n_out, int n_in, int K, int Cin, int Cout, float* dW,
                                         int accumulate, float* ws, size_t ws_floats, void* stream) {
+  if (dy_half & 2) {                                                   // pre-rounded rows of an f32 matrix: the f32-rows form's launch
+    if (x_half) return wgrad_bf16_launch<1, 1, true>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
+    return wgrad_bf16_launch<0, 1, true>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
+  }
   if (x_half && dy_half) return wgrad_bf16_launch<1, 1>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
   if (x_half) return wgrad_bf16_launch<1, 0>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
   if (dy_half) return wgrad_bf16_launch<0, 1>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
@@ -3000,7 +3010,7 @@ extern "C" size_t es_gen_transpose_wgrad_workspace_floats(const float* X, int ld
 extern "C" size_t es_spconv_wgrad_workspace_floats(int bf16, const void* X, int x_half, int ldx, const void* dY, int dy_half,
                                                    int ldy, int n_out, int n_in, int K, int Cin, int Cout) {
   if (n_out <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  WgradPlan p = bf16 ? wgrad_plan_bf16(x_half, dy_half, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, true)
+  WgradPlan p = bf16 ? wgrad_plan_bf16(x_half, (dy_half & 2) ? 0 : dy_half, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, true)
                      : wgrad_plan_f32(n_out, K, Cin, Cout, true);
   return p.splits > 1 ? (size_t)p.splits * K * Cin * Cout : 0;
 }

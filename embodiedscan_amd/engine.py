@@ -22,7 +22,7 @@ _NEW_VARS = None            # list while graphed() captures a segment
 class Var:
     """A row matrix (N, C) f32 on the device with an optional gradient (and lazily made bf16 shadows of both, the
     gather sources of the bf16 convolution kernels)."""
-    __slots__ = ('d', 'g', 'rg', 'dh', 'gh', 'gate', 'gated', 'fresh')
+    __slots__ = ('d', 'g', 'rg', 'dh', 'gh', 'gate', 'gated', 'fresh', 'gsh', 'fold')
 
     def __init__(self, d, rg=True):
         self.d, self.g, self.rg = d, None, rg
@@ -32,6 +32,9 @@ class Var:
         self.fresh = False      # True between conv() and the norm() that consumes its output (nobody else sees this Var)
         self.gate = None        # folded-BN scale of the fused conv+BN+ReLU that produced this Var (see conv_affine)
         self.gated = False      # True: .g already is the gradient w.r.t. the producer's (pre-BN) conv output
+        self.gsh = False        # True: the backward of the conv() that produced this Var reads .g through its bf16 shadow alone
+        self.fold = None        # folded-BN scale of the conv + BN (no activation) that produced this Var, when that layer's backward can take
+                                # the gradient of its conv output as pre-rounded bf16 rows (conv_affine: the downsample of a residual join)
 
     def shadow(self):
         if self.dh is None:
@@ -591,6 +594,25 @@ def _use_shadow(n_rows, C, K, cin, cout):
     return K > 1 and hip.raw('es_spconv_bf16_is_fast')(n_rows, C, K, cin, cout) == 1
 
 
+def _grad_shadow_only(x, w, n_out, need_dx, bf, gate=None, ldg=None):
+    """the backward of this convolution takes the bf16 shadow of its output gradient (leading dimension ldg; None: contiguous rows)
+    for both of its launches: _conv_wgrad and _conv_dgrad gather gh, and the f32 rows are read by a bias column sum at most"""
+    K, cin, cout = w.d.shape
+    return bool(bf and cout >= 16 and need_dx and x.rg and gate is None and (ldg is None or ldg == cout)
+                and _use_shadow(n_out, cout, K, cout, cin))
+
+
+# Gradient rows that only bf16 readers see are written once, in bf16 (A/B switch; 0: exactly the launches before it existed).  The
+# gradient a train-mode norm hands to the convolution that produced its input is such a matrix when that convolution's backward gathers
+# the shadow for both launches (_grad_shadow_only) and has no bias: es_norm_bwd then writes the shadow alone (dx = NULL), and the
+# convolution's .g IS that bf16 matrix.  The per-launch instrumentation records and reads the f32 rows: with any of it on they are written.
+GRAD_ROWS_BF16 = [os.environ.get('ES_GRAD_ROWS_BF16', '1') != '0']
+
+
+def _f32_grad_rows_wanted():
+    return DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None or hip.PROFILE is not None
+
+
 # ------------------------------------------------------------------ halo-tile K = 27 convolutions (round 6, csrc/halo.hip)
 HALO = [os.environ.get('ES_HALO', '1') != '0']
 if os.environ.get('ES_HALO_MIN_WGS') is not None:
@@ -652,6 +674,9 @@ def _ld(t):
 def _grad_target(v, shape_like):
     """(tensor, accumulate flag) for writing the gradient of v."""
     v.gh = None                                       # whatever shadow of the gradient exists is about to go stale
+    # (a bf16 .g is the only copy of a gradient whose producer promised a single consumer -- norm() on a fresh conv output, a join on
+    # its downsample identity: a second consumer would write f32 rows into it)
+    assert v.g is None or v.g.dtype == torch.float32, 'a second consumer accumulates into gradient rows that were written in bf16'
     if v.g is None:
         v.g = torch.empty(shape_like.shape, dtype=torch.float32, device=shape_like.device)    # gradients are f32 rows
         return v.g, 0
@@ -770,13 +795,16 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     TAPE.add(bwd)
     x.fresh = False
     y.fresh = True
+    y.gsh = TAPE.enabled and bias is None and _grad_shadow_only(x, w, n_out, need_dx, bf)
     return y
 
 
-def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, gate=None, dense=None, maps=None, img=None):
+def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, gate=None, dense=None, maps=None, img=None, pre16=False):
     """wgrad (+ bias grad) and dgrad of a convolution whose output gradient is the row matrix `gy`.
     gate: folded-BN scale of x's producer -- the dgrad launch then also applies that layer's ReLU mask and BN scale
-    (x is its only consumer), leaving x.g as the gradient of the producer's raw conv output."""
+    (x is its only consumer), leaving x.g as the gradient of the producer's raw conv output.
+    pre16: gy holds the PRE-ROUNDED bf16 rows of an f32 matrix that was never stored (conv_affine's joins, GRAD_ROWS_BF16): the K = 1
+    launches take them in place of that matrix, on its tiles and slices; whoever chose the bf16 rows has checked that they can."""
     K, cin, cout = w.d.shape
     rec = None
     # dense engine: weight gradient / data gradient by address arithmetic where the library takes the shape
@@ -792,27 +820,33 @@ def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, g
     # bf16 shadow of the output gradient: gather source of the data-gradient launch and, with the input's shadow from
     # the forward pass, of the weight-gradient launch (made here, before the weight-gradient stream forks)
     gh = None
-    if dn_w is not None or dn_d is not None or (
-            bf and cout >= 16 and need_dx and x.rg and gate is None and _ld(gy) == cout and _use_shadow(n_out, cout, K, cout, cin)):
+    if gy.dtype == torch.bfloat16:               # bf16 gradient rows (GRAD_ROWS_BF16: nothing reads this gradient in f32) are their own
+        assert bf and _ld(gy) == cout and bias is None              # shadow: no cast launch
+        if pre16:
+            assert K == 1 and x.d.dtype == torch.bfloat16
+        else:                                    # from norm(): both launches gather the shadow anyway
+            assert gy is y.g and _grad_shadow_only(x, w, n_out, need_dx, bf, gate)
+            gh = y.gh = gy
+    elif dn_w is not None or dn_d is not None or _grad_shadow_only(x, w, n_out, need_dx, bf, gate, _ld(gy)):
         gh = y.grad_shadow() if gy is y.g else _cast_rows(gy)
     if dn_w is not None:
         x.shadow()                               # (made by the forward launch; never on the weight-gradient stream)
     if w.g is not None or (bias is not None and bias.g is not None):
         sw = _wgrad_stream(gy, x.d, gh, x.dh)
     if w.g is not None:
-        _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw)
+        _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw, pre16)
     if bias is not None and bias.g is not None:
         # column sums of gy (round 4: one deterministic launch on the weight-gradient stream; was an f32 GEMM against a column of ones)
         nb, dst = cout - bias_from, bias.g.data_ptr() + 4 * bias_from
         ws, nf = stream_ws(sw, 'colsum', int(hip.raw('es_colsum_workspace_floats')(n_out, nb)), gy)
         call('es_colsum', gy.data_ptr() + 4 * bias_from, _ld(gy), n_out, nb, dst, _first_write(dst), P(ws), nf, sw)
     if need_dx and x.rg:
-        _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img)
+        _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img, pre16)
     if rec is not None and rec['need_dx']:
         rec['after'] = x.g.clone()               # (gradient buffer after this launch; `before` = what it accumulated onto)
 
 
-def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw):
+def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw, pre16=False):
     """the weight-gradient launch of a convolution on stream `sw`: the first candidate that takes it (a fast path's launcher has the
     last word on the operands: -4 passes on to the next candidate)"""
     K, cin, cout = w.d.shape
@@ -834,25 +868,28 @@ def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw):
                             P(ws), nf, sw):
                 return
     # 1x1 layers on contiguous rows (identity map): streaming kernel (csrc/imgwgrad.hip)
-    if xh_f32 and K == 1 and nbr is None and n_in == n_out:
+    if (xh_f32 or (pre16 and x.dh is not None)) and K == 1 and nbr is None and n_in == n_out:
         nf = int(hip.raw('es_rows_wgrad1_workspace_floats')(n_out, cin, cout))
         if nf:
             ws, nf = stream_ws(sw, 'wgrad', nf, gy)
-            if hip.try_call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g), acc, P(ws), nf, sw):
+            if hip.try_call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g), acc | (2 if pre16 else 0),
+                            P(ws), nf, sw):                      # (bit 1 of `accumulate`: bf16 gradient rows)
                 return
     # map kernels: gathering from the bf16 shadows where they exist (bf16 activation rows are their own shadow)
     if bf and (gh is not None or x.dh is not None or x.d.dtype == torch.bfloat16):
         xs, ys = x.dh if x.dh is not None else x.d, gh if gh is not None else gy
-        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), int(gh is not None), _ld(ys),
-               P(nbr), n_out, n_in, K, cin, cout, like=gy, acc=acc)
+        # (dy_half 3: pre-rounded rows on the plan of the f32 matrix they stand for; 1: a shadow)
+        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), 3 if pre16 else int(gh is not None),
+               _ld(ys), P(nbr), n_out, n_in, K, cin, cout, like=gy, acc=acc)
         return
     assert x.d.dtype == torch.float32, 'bf16 activation rows reach the weight gradient through their shadow (x.dh)'
     _wgrad('es_spconv_wgrad_bf16' if bf else 'es_spconv_wgrad', sw, P(w.g), P(x.d), _ld(x.d), P(gy), _ld(gy), P(nbr), n_out, n_in, K,
            cin, cout, like=gy, acc=acc)
 
 
-def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
-    """the data-gradient launch of a convolution into x.g: the first candidate that takes it (as _conv_wgrad).  gate: see _conv_backward"""
+def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img, pre16=False):
+    """the data-gradient launch of a convolution into x.g: the first candidate that takes it (as _conv_wgrad).  gate, pre16: see
+    _conv_backward"""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
     s = _stream()
@@ -874,8 +911,8 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
         if _is_mirror(inv):                      # the fused-epilogue entry points have no mirrored tap walk: the real inverse map
             inv = inv.real()
         if x.d.dtype == torch.bfloat16:          # the gate operand is the bf16 activation (only its sign is read)
-            call('es_spconv_fwd_bf16_io', P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
-                 P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
+            call('es_spconv_fwd_bf16_io', P(gy), int(gy.dtype == torch.bfloat16), _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin,
+                 P(gate), 0, P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
         else:
             call('es_spconv_fwd_bf16_affine', P(gy), _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
                  P(x.d), _ld(x.d), 3, P(x.g), _ld(x.g), s)
@@ -883,10 +920,13 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
     g, acc = _grad_target(x, x.d)
     # 1x1 / stride-2 image layer (downsample.0): a row GEMM over the gradient rows only, stored to the even pixels (k_img_dgrad1_s2)
     if (IMG_STRIDED_DGRAD[0] and img is not None and K == 1 and img[3] == 2 and bf and gh is None and dn_d is None
-            and gy.dtype == torch.float32 and g.dtype == torch.float32 and n_in == img[0] * img[1] * img[2]
+            and (gy.dtype == torch.float32 or pre16) and g.dtype == torch.float32 and n_in == img[0] * img[1] * img[2]
             and hip.raw('es_img_dgrad1_s2_supported')(img[0], img[1], img[2], cout, cin) == 1
-            and hip.try_call('es_img_dgrad1_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cout, cin, P(g), _ld(g), acc, s)):
+            and hip.try_call('es_img_dgrad1_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cout, cin, P(g), _ld(g),
+                             acc | (2 if pre16 else 0), s)):         # (bit 1 of `accumulate`: bf16 gradient rows)
         return
+    # pre-rounded rows reach an ungated data gradient only where that launch takes them (_pre16_ok, checked before they were chosen)
+    assert not pre16, 'pre-rounded gradient rows were chosen for a layer whose data gradient cannot take them'
     if dn_d is not None:                         # dense engine (dense_ok)
         if _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(g), _ld(g), acc, gh):
             return
@@ -905,14 +945,34 @@ def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img):
         call('es_spconv_fwd', P(gy), _ld(gy), P(w.d), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), 1, acc, s)
 
 
-def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=True, sole_consumer=False, out_bf16=False, img=None):
+def _pre16_ok(x, w, nbr, n_in, n_out, need_dx, gate, img):
+    """every backward launch of this K = 1 layer of the image backbone takes the gradient of its conv output as pre-rounded bf16 rows and
+    gives the bits of the f32 rows (GRAD_ROWS_BF16).  The conditions imply the launchers' acceptance -- there is no way back to f32 rows once
+    the join has written bf16: bf16 activation rows (never the small-linear weight-gradient plan, which reads f32), cout % 8 on fresh
+    contiguous rows (the alignment dy_half = 3 and the stride-2 kernel ask for), and a data gradient that is the gated K = 1 row GEMM, the
+    stride-2 image kernel on a grid it supports, or absent."""
+    K, cin, cout = w.d.shape
+    if not (K == 1 and x.d.dtype == torch.bfloat16 and _ld(x.d) == cin and cout % 8 == 0):
+        return False
+    if not (need_dx and x.rg):
+        return True
+    if gate is not None:
+        return nbr is None and n_in == n_out
+    return bool(IMG_STRIDED_DGRAD[0] and img is not None and img[3] == 2 and n_in == img[0] * img[1] * img[2]
+                and hip.raw('es_img_dgrad1_s2_supported')(img[0], img[1], img[2], cout, cin) == 1)
+
+
+def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=True, sole_consumer=False, out_bf16=False, img=None,
+                res_sole=False):
     """conv -> frozen-BN affine (+ residual) (+ ReLU) of the 2-D backbone.  In bf16 mode this is ONE launch (affine
     fused into the conv epilogue); in f32 mode conv() followed by affine_act().
     sole_consumer: promise that x feeds nothing but this conv; if x itself came out of a fused conv+BN+ReLU, its
     ReLU/BN backward is then folded into this conv's data-gradient launch.
     out_bf16: store the output rows in bf16 (the image backbone's activations); x / res may themselves be bf16 row matrices.
     img: (n_img, H, W, stride) when the map is a 3x3 / pad 1 (or 1x1 / pad 0) image-grid map: the weight gradient (csrc/imgwgrad.hip) and
-    the data gradient (csrc/imgconv.hip) may then run by address arithmetic instead of through the map."""
+    the data gradient (csrc/imgconv.hip) may then run by address arithmetic instead of through the map.
+    res_sole: promise that res feeds nothing but this layer (the downsample identity of a bottleneck): where res came out of a conv + BN
+    without activation, the join's backward then writes the gradient of THAT conv output itself (GRAD_ROWS_BF16)."""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
     if PRECISION[0] != 'bf16':
@@ -947,23 +1007,40 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
     if act == 1 and res is None:
         y.gate = scale
     gate = x.gate if sole_consumer else None
+    if act == 0 and res is None and y16 and TAPE.enabled and _pre16_ok(x, w, nbr, n_in, n_out, need_dx, gate, img):
+        y.fold = scale
 
     def bwd():
         if y.g is None:
             return
         if DEBUG_GRADS is not None:
             DEBUG_GRADS[id(y)] = y.g.clone()
-        if y.gated:                             # the consumer's dgrad launch already applied mask and scale
+        if y.gated:                             # the consumer's launch already applied mask and scale (a gated dgrad; a join: bf16 rows)
             gconv = y.g
         else:
-            gr = accr = 0
-            if res is not None and res.rg:
-                t, accr = _grad_target(res, res.d)
-                gr = P(t)
-            gconv = torch.empty((n_out, cout), dtype=torch.float32, device=y.d.device)   # gradient w.r.t. the conv output
-            call('es_affine_act_bwd_yh' if y.d.dtype == h16 else 'es_affine_act_bwd', P(y.g), P(y.d), P(scale), n_out, cout, act,
-                 P(gconv), 0, gr, accr, _stream())
-        _conv_backward(x, w, nbr, inv, n_out, y, gconv, None, 0, need_dx, True, gate, img=img)
+            # residual joins of the image backbone (conv3 + bn3 + identity -> ReLU, bf16 activations): both readers of the conv-output
+            # gradient -- conv3's gated K = 1 data gradient and its weight gradient -- round it to bf16 on load, so it is written in
+            # bf16 here (GRAD_ROWS_BF16; same es_pack_bf16, the gradients keep their bits).  Other layers: f32 rows as before.
+            rows16 = (GRAD_ROWS_BF16[0] and res is not None and y.d.dtype == h16 and act in (0, 1) and not _f32_grad_rows_wanted()
+                      and _pre16_ok(x, w, nbr, n_in, n_out, need_dx, gate, img))
+            # ... and on a downsample block, where the identity is a conv + BN output nothing else reads, the gradient of that conv
+            # output too (dz * its fold, what its own act = 0 backward launch would make of an f32 dres): no dres, no such launch
+            two = rows16 and res_sole and res.fold is not None and res.rg and res.g is None and res.d.shape == y.d.shape
+            gconv = torch.empty((n_out, cout), dtype=h16 if rows16 else torch.float32, device=y.d.device)   # gradient w.r.t. the conv output
+            if two:
+                res.g, res.gated = torch.empty((n_out, cout), dtype=h16, device=y.d.device), True
+                call('es_affine_act_bwd_yh_xh2', P(y.g), P(y.d), P(scale), P(res.fold), n_out, cout, act, P(gconv), P(res.g), _stream())
+            else:
+                gr = accr = 0
+                if res is not None and res.rg:
+                    t, accr = _grad_target(res, res.d)
+                    gr = P(t)
+                if rows16:
+                    call('es_affine_act_bwd_yh_xh', P(y.g), P(y.d), P(scale), n_out, cout, act, P(gconv), gr, accr, _stream())
+                else:
+                    call('es_affine_act_bwd_yh' if y.d.dtype == h16 else 'es_affine_act_bwd', P(y.g), P(y.d), P(scale), n_out, cout,
+                         act, P(gconv), 0, gr, accr, _stream())
+        _conv_backward(x, w, nbr, inv, n_out, y, gconv, None, 0, need_dx, True, gate, img=img, pre16=gconv.dtype == h16)
     TAPE.add(bwd)
     return y
 
@@ -1113,10 +1190,16 @@ def norm(x, weight, bias, seg_off, eps, act=0, res=None, running=None, momentum=
         if DEBUG_GRADS is not None:
             DEBUG_GRADS[id(y)] = y.g.clone()
         ws2 = empty((ws_n,), x.d)
-        g, acc = _grad_target(x, x.d)
-        gh = empty((n, C), x.d, dtype=torch.bfloat16) if (fuse and private and _ld(g) == C) else None
-        call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
-             P(weight.d), act, P(weight.g), P(bias.g), P(ws2), P(g), _ld(g), acc, P(gh), s)
+        if GRAD_ROWS_BF16[0] and fuse and private and x.gsh and x.g is None and not _f32_grad_rows_wanted():
+            # the producing convolution's backward gathers the shadow only: no f32 rows (GRAD_ROWS_BF16)
+            x.g = gh = empty((n, C), x.d, dtype=torch.bfloat16)
+            call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
+                 P(weight.d), act, P(weight.g), P(bias.g), P(ws2), 0, C, 0, P(gh), s)
+        else:
+            g, acc = _grad_target(x, x.d)
+            gh = empty((n, C), x.d, dtype=torch.bfloat16) if (fuse and private and _ld(g) == C) else None
+            call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
+                 P(weight.d), act, P(weight.g), P(bias.g), P(ws2), P(g), _ld(g), acc, P(gh), s)
         x.gh = gh
         if DEBUG_GRADS is not None:
             DEBUG_GRADS[('norm', id(y))] = dict(dx=g.clone(), dz=y.g.clone(), mean=mean.clone(), invstd=invstd.clone(),

@@ -181,7 +181,7 @@ class ResNet:
                 else:
                     idt = cur
                 cur = E.conv_affine(o, self._par(p + 'conv3.weight'), None, None, n_out, *self.fold[p + 'bn3'], act=1,
-                                    res=idt, sole_consumer=True, out_bf16=a16)
+                                    res=idt, sole_consumer=True, out_bf16=a16, res_sole=bi == 0)
                 if not E.TAPE.enabled:
                     cur.rg = False
             if li in self.out_indices:

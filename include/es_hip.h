@@ -228,7 +228,10 @@ int es_spconv_wgrad_bf16(const float* X, int ldx, const float* dY, int ldy, cons
 /* Same operator with either operand taken from a bf16 copy ("shadow", es_cast_rows_bf16) of the row matrix: x_half /
  * dy_half non-zero -> X / dY point at (n, ld) bf16 rows (ld in elements).  Results are bit-identical to
  * es_spconv_wgrad_bf16 on the f32 originals when both launches use the same tile and slices (the f32 path rounds to the
- * same bf16 values while staging); the gathered bytes halve. */
+ * same bf16 values while staging); the gathered bytes halve.
+ * dy_half = 3: dY holds the PRE-ROUNDED bf16 rows of an f32 gradient matrix that was never stored (es_affine_act_bwd_yh_xh): tile, slices
+ * and kernel family are those of dy_half = 0 on that f32 matrix with the same ldy, so the result is that launch's bit for bit (dy_half = 1
+ * may pick the tiles only a pair of shadows can feed).  ldy % 8 != 0, dY not 16-byte aligned or the small-linear plan: -4, nothing written. */
 int es_spconv_wgrad_bf16_src(const void* X, int x_half, int ldx, const void* dY, int dy_half, int ldy, const int* nbr,
                              int n_out, int n_in, int K, int Cin, int Cout, float* dW, int accumulate, float* ws,
                              size_t ws_floats, void* stream);
@@ -249,7 +252,10 @@ int es_norm_fwd(const float* x, int ldx, int n, int C, const int* seg_off_host, 
                 void* y_bf16, void* stream);
 /* y_bf16 / dx_bf16 (0 = none): a dense (n, C) bf16 copy of the rows the apply pass has just computed, written by the same
  * pass -- the gather source ("shadow") of the bf16 convolution that consumes them; bit-identical to es_cast_rows_bf16 of
- * y / dx.  dy is overwritten with the pre-activation gradient (== gradient of the residual input). */
+ * y / dx.  dy is overwritten with the pre-activation gradient (== gradient of the residual input).
+ * es_norm_bwd with dx = NULL and dx_bf16 given: the bf16 rows are the only output of the apply pass (every reader of the gradient
+ * takes the shadow) -- the f32 store is skipped, dx_bf16, dweight, dbias and dz keep their bits; ldo is ignored.  dx = NULL with
+ * accumulate != 0 or without dx_bf16: -2, nothing is written. */
 int es_norm_bwd(float* dy, int ldd, const float* y, int ldy, const float* x, int ldx, int n, int C,
                 const int* seg_off_host, int nseg, const float* mean, const float* invstd, const float* weight,
                 int act, float* dweight, float* dbias, float* workspace, float* dx, int ldo, int accumulate,
@@ -291,6 +297,16 @@ int es_affine_act_bwd(const float* dy, const float* y, const float* scale, size_
  * (8-byte y_bf16), else -7.  act = 2 returns -2: y + 1 cannot be taken from a bf16 y to f32 accuracy.  Nothing is written on refusal. */
 int es_affine_act_bwd_yh(const float* dy, const void* y_bf16, const float* scale, size_t n, int C, int act, float* dx,
                          int acc_x, float* dres, int acc_r, void* stream);
+/* es_affine_act_bwd_yh with dx written as bf16 rows (n, C): bit for bit the es_cast_rows_bf16 of the f32 dx that entry point stores
+ * with acc_x = 0 -- for a gradient whose only readers are bf16 matrix-core launches (the residual joins of the image backbone: conv3's
+ * data and weight gradient).  dres (may be NULL) stays f32 as there.  dx_bf16 NULL or act = 2: -2; alignment as above (8-byte dx_bf16): -7.
+ * es_affine_act_bwd_yh_xh2: the join of a downsample block, whose identity is the output of a 1x1 convolution + frozen BN (no activation)
+ * that nothing else reads: besides dx_bf16 = r(dz * scale) it writes dx2_bf16 = r(dz * scale2), the gradient of THAT convolution's output
+ * -- bit for bit the rounded output of the act = 0 es_affine_act_bwd_yh launch on dres that it replaces -- and no dres. */
+int es_affine_act_bwd_yh_xh(const float* dy, const void* y_bf16, const float* scale, size_t n, int C, int act, void* dx_bf16,
+                            float* dres, int acc_r, void* stream);
+int es_affine_act_bwd_yh_xh2(const float* dy, const void* y_bf16, const float* scale, const float* scale2, size_t n, int C, int act,
+                             void* dx_bf16, void* dx2_bf16, void* stream);
 
 /* ---- A8 projection fusion.  point_fusion.py:208-311 ----------------------------------------------- */
 /* per-sample meta block layout (floats) */
@@ -778,7 +794,9 @@ int es_img_wgrad_set_option(int key, int value);
  * (n x ldy) f32 gradient rows (rounded to bf16 in the kernel) -- Bottleneck.conv1 / conv3 of the image backbone.  Channel counts: multiples
  * of 64 up to 512, or 32 against >= 64; taken from 256 input channels or from 500 000 rows (es_img_wgrad_set_option 43), where it beats
  * the ring kernel.  es_rows_wgrad1_workspace_floats returns 0 for a shape it does not take (the caller keeps
- * es_spconv_wgrad_bf16_src); -4 / -5 as above.  Partial tensors per row slice, added in slice order: bit-reproducible. */
+ * es_spconv_wgrad_bf16_src); -4 / -5 as above.  Partial tensors per row slice, added in slice order: bit-reproducible.
+ * Bit 1 of `accumulate` (value 2): dY points at bf16 rows (ldy in elements) holding the pre-rounded values of that f32 matrix
+ * (es_affine_act_bwd_yh_xh) -- same tiles, slices and summation order, the f32 form's result bit for bit. */
 size_t es_rows_wgrad1_workspace_floats(int n, int Cin, int Cout);
 int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n, int Cin, int Cout, float* dW, int accumulate, float* ws,
                         size_t ws_floats, void* stream);
@@ -809,7 +827,8 @@ int es_img_conv_set_option(int key, int value);
  * es_img_dgrad1_s2_bf16: data gradient of a 1x1 / stride-2 layer -- es_spconv_fwd_bf16 on the 1-wide inverse map:
  *   dX[(im, 2 oy, 2 ox)] (+)= G[(im, oy, ox)] . W^T, G (x ldg) f32 rows of Cg channels, W_bf16 = the natural [Cx][Cg] copy, dX (x ldx) f32 rows
  *   of Cx channels; Cg, Cx multiples of 32.  accumulate 0: the same launch stores zeros to the three other pixels of every 2x2 cell;
- *   accumulate 1: they are not touched.
+ *   accumulate 1: they are not touched.  Bit 1 of `accumulate` (value 2): G points at bf16 rows (ldg in elements, a multiple of 8) holding
+ *   the pre-rounded values of that f32 matrix (es_affine_act_bwd_yh_xh) -- same tiles, chunks and sums, the f32 form's result bit for bit.
  * The _supported queries answer for fresh contiguous operands; the launchers apply the same check (even H / W, leading dimensions multiples
  * of 4, 16-byte aligned pointers, rows x ld < 2^31) to the operands they are given and return -4, writing nothing, where it fails.
  * es_img_stride_set_option: 52 on / off, 53 workgroups aimed for by the 3x3 kernel. */
