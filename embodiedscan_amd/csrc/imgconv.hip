@@ -567,7 +567,7 @@ extern "C" int es_img_dgrad1_s2_supported(int n_img, int H, int W, int Cg, int C
 
 extern "C" int es_img_dgrad1_s2_bf16(const float* G, int ldg, const void* Wn_bf16, int n_img, int H, int W, int Cg, int Cx, float* dX, int ldx,
                                      int accumulate, void* stream) {
-  const bool gh = (accumulate & 2) != 0;       // bit 1: G holds bf16 rows, the pre-rounded values of the f32 matrix (ldg in elements)
+  const bool gh = (accumulate & ES_ACC_ROWS_BF16) != 0;       // bit 1: G holds bf16 rows, the pre-rounded values of the f32 matrix (ldg in elements)
   accumulate &= 1;
   if (!img_dgrad1_s2_check(n_img, H, W, Cg, Cx, G, ldg, Wn_bf16, dX, ldx)) return -4;
   if (G == nullptr || Wn_bf16 == nullptr || dX == nullptr || (gh && (ldg % 8))) return -4;

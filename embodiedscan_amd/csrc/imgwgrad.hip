@@ -347,7 +347,7 @@ extern "C" size_t es_rows_wgrad1_workspace_floats(int n, int Cin, int Cout) {
 extern "C" int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n, int Cin, int Cout, float* dW, int accumulate,
                                    float* ws, size_t ws_floats, void* stream) {
   int ci, co, slices, rows;
-  const bool yh = (accumulate & 2) != 0;      // bit 1: dY holds bf16 rows, the pre-rounded values of the f32 matrix (ldy in elements)
+  const bool yh = (accumulate & ES_ACC_ROWS_BF16) != 0;      // bit 1: dY holds bf16 rows, the pre-rounded values of the f32 matrix (ldy in elements)
   accumulate &= 1;
   if (!rows_wgrad_check(n, Cin, Cout, Xh, ldx, dY, ldy, ci, co, slices, rows)) return -4;
   if (slices > 1 && (ws == nullptr || ws_floats < (size_t)slices * Cin * Cout)) return -5;

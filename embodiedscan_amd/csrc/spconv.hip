@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_spconv(const float* __restrict__ X, int
 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int row0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int mirror = accumulate & 2;                         // (bit 1 of the entry point's `accumulate`: mirrored tap walk)
+  const int mirror = accumulate & ES_ACC_MIRROR;                         // (bit 1 of the entry point's `accumulate`: mirrored tap walk)
   accumulate &= 1;
   const bool vecA = ((ldx & 3) == 0) && ((((uintptr_t)X) & 15) == 0);
   const bool vecB = TRANS_W ? (((Cin & 3) == 0) && ((((uintptr_t)W) & 15) == 0))
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void k_spconv_narrow_fwd(const float* __restri
   __shared__ int idxS[NW_ROWS * 27];
   __shared__ int maskS[NW_ROWS];
   const int t = threadIdx.x, co = t & 63, wv = t >> 6;
-  const int mirror = accumulate & 2;                         // (bit 1 of the entry point's `accumulate`)
+  const int mirror = accumulate & ES_ACC_MIRROR;                         // (bit 1 of the entry point's `accumulate`)
   accumulate &= 1;
   float w[27][CIN];
 #pragma unroll
@@ -364,7 +364,7 @@ extern "C" int es_spconv_fwd(const float* X, int ldx, const float* W, const int*
                              void* stream) {
   if (n_out <= 0 || Cout <= 0) return 0;
   if (K > MAXK) return -2;
-  if ((accumulate & 2) && (!(K & 1) || nbr == nullptr)) return -3;     // mirrored tap walk: an odd kernel on a real map
+  if ((accumulate & ES_ACC_MIRROR) && (!(K & 1) || nbr == nullptr)) return -3;     // mirrored tap walk: an odd kernel on a real map
   if (!trans_w && narrow_ok(nbr, K, Cin, Cout)) {
     const int tiles = es_cdiv(n_out, NW_ROWS);
     hipLaunchKernelGGL(k_spconv_narrow_fwd<3>, dim3(tiles > 2048 ? 2048 : tiles), dim3(256), 0, (hipStream_t)stream, X, ldx, W, nbr,
@@ -1995,7 +1995,7 @@ static int spconv_fwd_bf16_impl(const void* Xv, int x_is_bf16, int ldx, const vo
                                 int y_half = 0, int r_half = 0) {
   if (n_out <= 0 || Cout <= 0) return 0;
   if (K > MAXK) return -2;
-  const int mirror = accumulate & 2;                                   // bit 1: mirrored tap walk (ES_IO_MIRROR)
+  const int mirror = accumulate & ES_ACC_MIRROR;                                   // bit 1: mirrored tap walk (ES_IO_MIRROR)
   accumulate &= 1;
   if (mirror && (!(K & 1) || nbr == nullptr)) return -3;
   int io = (mirror ? ES_IO_MIRROR : 0) | (y_half ? ES_IO_Y16 : 0) | ((r_half && ep_res) ? ES_IO_R16 : 0) | (y_half & 0xff00);   // (bits 8-15: dev ablation switches of k_rowgemm2_bf16, tools/bench_rowgemm.py)
@@ -2957,7 +2957,7 @@ extern "C" int es_spconv_wgrad_bf16(const float* X, int ldx, const float* dY, in
 extern "C" int es_spconv_wgrad_bf16_src(const void* X, int x_half, int ldx, const void* dY, int dy_half, int ldy,
                                         const int* nbr, int n_out, int n_in, int K, int Cin, int Cout, float* dW,
                                         int accumulate, float* ws, size_t ws_floats, void* stream) {
-  if (dy_half & 2) {                                                   // pre-rounded rows of an f32 matrix: the f32-rows form's launch
+  if (dy_half & (ES_ROWS_PRE16 ^ ES_ROWS_BF16)) {                      // pre-rounded rows of an f32 matrix: the f32-rows form's launch
     if (x_half) return wgrad_bf16_launch<1, 1, true>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
     return wgrad_bf16_launch<0, 1, true>(X, ldx, dY, ldy, nbr, n_out, n_in, K, Cin, Cout, dW, accumulate, ws, ws_floats, stream);
   }
@@ -3010,7 +3010,7 @@ extern "C" size_t es_gen_transpose_wgrad_workspace_floats(const float* X, int ld
 extern "C" size_t es_spconv_wgrad_workspace_floats(int bf16, const void* X, int x_half, int ldx, const void* dY, int dy_half,
                                                    int ldy, int n_out, int n_in, int K, int Cin, int Cout) {
   if (n_out <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  WgradPlan p = bf16 ? wgrad_plan_bf16(x_half, (dy_half & 2) ? 0 : dy_half, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, true)
+  WgradPlan p = bf16 ? wgrad_plan_bf16(x_half, (dy_half & (ES_ROWS_PRE16 ^ ES_ROWS_BF16)) ? ES_ROWS_F32 : dy_half, X, ldx, dY, ldy, n_out, n_in, K, Cin, Cout, true)
                      : wgrad_plan_f32(n_out, K, Cin, Cout, true);
   return p.splits > 1 ? (size_t)p.splits * K * Cin * Cout : 0;
 }

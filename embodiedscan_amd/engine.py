@@ -6,14 +6,30 @@ Every forward function registers one closure on the tape; `TAPE.backward()` repl
 reverse.  Gradients w.r.t. parameters accumulate straight into the flat gradient arena.
 """
 import os
+from collections import namedtuple
 
 import torch
 from . import hip
 from .hip import P, call, iarr
 
+_C = hip.CONSTS             # the flag values of the C ABI by their names (include/es_hip.h)
+
 
 def _stream():
     return hip.stream()
+
+
+def _switch(env):
+    """an A/B switch as a one-element list (tests and tools set X[0]): on unless the environment says ES_X=0"""
+    return [os.environ.get(env, '1') != '0']
+
+
+def instrumented(fwd=True):
+    """Per-launch instrumentation is on: a profile (hip.PROFILE), a record hook of BACKWARD launches (DEBUG_CONV / DEBUG_GRADS / DEBUG_OPS) or,
+    with fwd, the hook of forward launches (DEBUG_FWD).  graphed() asks with DEBUG_FWD: a replayed forward would record nothing;
+    _f32_grad_rows_wanted() without: a forward record reads no gradient rows, so it has no say in how they are stored."""
+    return (hip.PROFILE is not None or DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None
+            or (fwd and DEBUG_FWD is not None))
 
 
 _NEW_VARS = None            # list while graphed() captures a segment
@@ -186,7 +202,7 @@ class no_tape:
 # a sequence once into a hipGraph (torch.cuda.CUDAGraph: activations live in the graph's private pool) and replays it with ONE
 # launch per step; the backward closures the sequence put on the tape are kept and re-registered at every replay (they run
 # eagerly, on the same buffers), the gradient fields of the sequence's Vars are reset first.
-GRAPHS = [os.environ.get('ES_GRAPHS', '1') != '0']
+GRAPHS = _switch('ES_GRAPHS')
 GRAPH_STATS = dict(captured=0, replayed=0, eager=0, failed=0)
 
 
@@ -208,9 +224,7 @@ def graphed(cache, key, fn):
     shadows; 2nd: captured, then replayed).  Eager whenever per-launch instrumentation is on, on the default stream (capture
     needs a non-default stream: the side stream of the two-stream schedule), or after a failed capture."""
     global _NEW_VARS
-    instrumented = (hip.PROFILE is not None or DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None
-                    or DEBUG_FWD is not None)
-    if not GRAPHS[0] or instrumented or _NEW_VARS is not None or \
+    if not GRAPHS[0] or instrumented() or _NEW_VARS is not None or \
             torch.cuda.current_stream() == torch.cuda.default_stream():
         GRAPH_STATS['eager'] += 1
         return fn()
@@ -267,7 +281,7 @@ def graphed(cache, key, fn):
 # (1) the side stream always starts ordered after everything queued on the main stream (fork event), (2) the main stream
 # joins before it touches anything the side stream produced, (3) tensors crossing streams stay referenced until the
 # join, so a block is only recycled by its own stream after the other stream's readers were ordered before it.
-TWO_STREAMS = [os.environ.get('ES_TWO_STREAMS', '1') != '0']
+TWO_STREAMS = _switch('ES_TWO_STREAMS')
 _SIDE = {}
 
 
@@ -305,7 +319,7 @@ def join_side():
 # Weight gradients hang off the backward chain (nothing downstream reads them before the optimiser), so they are
 # launched on a second stream paired with the compute stream: the chain of data-gradient launches does not wait for them
 # and under-filled launches of both kinds overlap.
-WGRAD_ASYNC = [os.environ.get('ES_WGRAD_ASYNC', '1') != '0']
+WGRAD_ASYNC = _switch('ES_WGRAD_ASYNC')
 _WGRAD_STREAMS = {}     # compute-stream handle -> dict(s=torch Stream, h=handle, fork=Event, join=Event, used=bool)
 _KEEP = []              # temporaries read by queued weight-gradient launches; released by the final join
 
@@ -420,27 +434,23 @@ def _wgrad(name, sw, dW, *args, like=None, acc=None):
     """launch a weight-gradient entry point (`args` = everything between the function name and dW) on stream `sw` with the
     workspace its row split asks for (that stream's 'wgrad' buffer); like: a tensor on the launch's device (None: the current GPU,
     for callers that hold raw pointers only); acc: the accumulate flag (None: _first_write(dW))"""
-    if name == 'es_spconv_wgrad_bf16_src':
-        X, xh, ldx, dY, yh, ldy, nbr, n_out, n_in, K, cin, cout = args
-        need = hip.raw('es_spconv_wgrad_workspace_floats')(1, X, xh, ldx, dY, yh, ldy, n_out, n_in, K, cin, cout)
-    else:
-        X, ldx, dY, ldy, nbr, n_out, n_in, K, cin, cout = args
-        need = hip.raw('es_spconv_wgrad_workspace_floats')(int(name == 'es_spconv_wgrad_bf16'), X, 0, ldx, dY, 0, ldy, n_out, n_in,
-                                                           K, cin, cout)
+    f32 = _C['ES_ROWS_F32']        # (the workspace query takes the operand kinds of the _src form; the other two entry points read f32 rows)
+    X, xh, ldx, dY, yh, ldy, nbr, *shape = args if name == 'es_spconv_wgrad_bf16_src' else (args[0], f32, args[1], args[2], f32, *args[3:])
+    need = hip.raw('es_spconv_wgrad_workspace_floats')(int(name != 'es_spconv_wgrad'), X, xh, ldx, dY, yh, ldy, *shape)
     if like is None:
         like = torch.empty(0, device=torch.device('cuda', torch.cuda.current_device()))
     ws, nf = stream_ws(sw, 'wgrad', need, like) if need else (None, 0)
     call(name, *args, dW, _first_write(dW) if acc is None else acc, P(ws), nf, sw)
 
 
-IMG_WGRAD = [os.environ.get('ES_IMG_WGRAD', '1') != '0']     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
+IMG_WGRAD = _switch('ES_IMG_WGRAD')     # round 6: 3x3 image weight gradients on csrc/imgwgrad.hip (A/B switch)
 # stride-2 data gradients of the image backbone by address arithmetic (csrc/imgconv.hip: es_img_dgrad3_s2_bf16 / es_img_dgrad1_s2_bf16),
 # bit-identical to the map-kernel launches they replace (A/B switch and the way back)
-IMG_STRIDED_DGRAD = [os.environ.get('ES_IMG_STRIDED_DGRAD', '1') != '0']
+IMG_STRIDED_DGRAD = _switch('ES_IMG_STRIDED_DGRAD')
 # FCAF3D head backward without the work its result does not need (A/B switch; off: exactly the launches before it existed): the 8 taps of a
 # generative transposed convolution's weight gradient in one launch (es_gen_transpose_wgrad_bf16), the head gradient matrix cleared by the
 # focal-loss launch instead of a zero fill (es_focal_loss_clear, models/dense_heads/fcaf3d_head.py)
-HEAD_BWD_FUSED = [os.environ.get('ES_HEAD_BWD_FUSED', '1') != '0']
+HEAD_BWD_FUSED = _switch('ES_HEAD_BWD_FUSED')
 
 
 # Python's cyclic collector and the train loop (round 5, profiles/r5d / r5f_bench_grounding_diag.json: `gc_collections`): a generation-2
@@ -451,8 +461,6 @@ HEAD_BWD_FUSED = [os.environ.get('ES_HEAD_BWD_FUSED', '1') != '0']
 # this image: a full collection of 10^6 tracked objects 180 ms -> 0.0 ms after the freeze).  ES_GC_FREEZE=0 turns this off; a process
 # that drops a detector and builds another should gc.unfreeze() + gc.collect() in between (bench.py release_frozen).
 GC_SETTLE_STEP = 6
-
-
 _HOST_SETTLED = [False]
 
 
@@ -485,7 +493,7 @@ def settle_gc(det):
     settle_host_threads()
     n = getattr(det, '_steps_done', 0) + 1
     det._steps_done = n
-    if n == GC_SETTLE_STEP and os.environ.get('ES_GC_FREEZE', '1') != '0':
+    if n == GC_SETTLE_STEP and _switch('ES_GC_FREEZE')[0]:
         import gc
         gc.collect()
         gc.freeze()
@@ -509,8 +517,6 @@ def drop_caches():
 
 
 MARKS = None            # bench.py sets a list: stage boundaries as (name, event) recorded on the current stream
-
-
 HOST_MARKS = None       # tools/host_profile.py sets a list: (name, host perf_counter) at the same stage boundaries
 
 
@@ -562,8 +568,8 @@ def _cast_rows(t):
     return h
 
 
-GEN_FUSED = [os.environ.get('ES_GEN_FUSED', '1') != '0']          # generative transposed conv: 8 taps in one launch per direction (round 4:
-                                                                  # run on hardware, forward bit-identical, step -0.6 ms; profiles/r4a_*)
+GEN_FUSED = _switch('ES_GEN_FUSED')        # generative transposed conv: 8 taps in one launch per direction (round 4:
+                                           # run on hardware, forward bit-identical, step -0.6 ms; profiles/r4a_*)
 
 
 def _split_ws(n_out, K, cin, cout, like):
@@ -582,11 +588,9 @@ def _split_ws(n_out, K, cin, cout, like):
 def _fwd_bf16(X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, like):
     """es_spconv_fwd_bf16 with the deterministic-split workspace when the launch would split its tap list -> the entry point taken"""
     ws, nf = _split_ws(n_out, K, cin, cout, like)
-    if ws is not None:
-        call('es_spconv_fwd_bf16_ws', X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, P(ws), nf, _stream())
-        return 'es_spconv_fwd_bf16_ws'
-    call('es_spconv_fwd_bf16', X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, _stream())
-    return 'es_spconv_fwd_bf16'
+    entry, ws_args = ('es_spconv_fwd_bf16', ()) if ws is None else ('es_spconv_fwd_bf16_ws', (P(ws), nf))
+    call(entry, X, x_is_bf16, ldx, Wp, nbr, n_out, n_in, K, cin, cout, bias_p, Y, ldy, acc, *ws_args, _stream())
+    return entry
 
 
 def _use_shadow(n_rows, C, K, cin, cout):
@@ -606,15 +610,15 @@ def _grad_shadow_only(x, w, n_out, need_dx, bf, gate=None, ldg=None):
 # gradient a train-mode norm hands to the convolution that produced its input is such a matrix when that convolution's backward gathers
 # the shadow for both launches (_grad_shadow_only) and has no bias: es_norm_bwd then writes the shadow alone (dx = NULL), and the
 # convolution's .g IS that bf16 matrix.  The per-launch instrumentation records and reads the f32 rows: with any of it on they are written.
-GRAD_ROWS_BF16 = [os.environ.get('ES_GRAD_ROWS_BF16', '1') != '0']
+GRAD_ROWS_BF16 = _switch('ES_GRAD_ROWS_BF16')
 
 
 def _f32_grad_rows_wanted():
-    return DEBUG_CONV is not None or DEBUG_GRADS is not None or DEBUG_OPS is not None or hip.PROFILE is not None
+    return instrumented(fwd=False)
 
 
 # ------------------------------------------------------------------ halo-tile K = 27 convolutions (round 6, csrc/halo.hip)
-HALO = [os.environ.get('ES_HALO', '1') != '0']
+HALO = _switch('ES_HALO')
 if os.environ.get('ES_HALO_MIN_WGS') is not None:
     hip.raw('es_halo_set_option')(30, int(os.environ['ES_HALO_MIN_WGS']))
 if os.environ.get('ES_HALO_PLAN_BITMAP') is not None:       # A/B switch of the bitmap halo plan (default: on; 0: hash-and-rank)
@@ -683,6 +687,25 @@ def _grad_target(v, shape_like):
     return v.g, 1
 
 
+def _grad_ptr(v):
+    """_grad_target as (pointer, accumulate flag) for a launch with optional outputs: (0, 0) for no Var or one that takes no gradient"""
+    if v is None or not v.rg:
+        return 0, 0
+    t, acc = _grad_target(v, v.d)
+    return P(t), acc
+
+
+def _grad_give(v, t, alias=True):
+    """give the f32 row matrix `t` to v as its gradient: v has none yet -> t itself where the caller says v may alias it (nobody else keeps
+    or writes t), else a copy -> True; v has one -> added to it (es_axpy2d) -> False.  The same guards as _grad_target."""
+    v.gh = None
+    assert v.g is None or v.g.dtype == torch.float32, 'a second consumer accumulates into gradient rows that were written in bf16'
+    if v.g is None:
+        v.g = t if alias else t.clone()
+        return True
+    call('es_axpy2d', P(v.g), _ld(v.g), P(t), _ld(t), t.shape[0], t.shape[1], 1.0, 1, _stream())
+    return False
+
 
 # ------------------------------------------------------------------ dense-volume convolutions (round 5, csrc/dconv.hip)
 # nn.Conv3d on a dense (B, X, Y, Z) grid by address arithmetic: no neighbour map.  `dense` = (B, X, Y, Z, ksize, stride, pad) of the
@@ -690,7 +713,7 @@ def _grad_target(v, shape_like):
 # channels % 64, output channels % 256; the data gradient for stride 1) and falls back to the map kernels elsewhere -- `maps` is then
 # a callable returning (nbr, inv), so the maps of a layer the dense engine covers completely are never built.
 # Z = 0 names a FLAT grid: nn.Conv2d on (B, X, Y) images (the FPN's 3x3 output convolutions); a bias is pre-filled, the launch accumulates.
-DENSE = [os.environ.get('ES_DENSE', '1') != '0']
+DENSE = _switch('ES_DENSE')
 
 
 def _dense_geom(dense):
@@ -746,6 +769,7 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     dense / maps: see "dense-volume convolutions" above (nbr / inv are then taken from maps() where a map kernel runs)."""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
+    bias_p = P(bias.d) if bias else 0
     y = Var(empty((n_out, cout), x.d))
     bf = PRECISION[0] == 'bf16' and cin >= 16
     if maps is not None:
@@ -757,28 +781,22 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     dn = bf and _ld(x.d) == cin and dense_ok(dense, 0, cin, cout)
     if dn and bias:                               # rows pre-filled with the bias, the launch accumulates (the tile's accumulators fill the
         y.d.copy_(bias.d.expand_as(y.d))          # register file: an epilogue that also held the bias spilled)
-    gathered = True                                # the launch gathers x's bf16 shadow (False: the f32 rows)
     if dn and _dense_launch(P(x.shadow()), cin, P(w.bf16()[1]), dense, 0, cin, cout, P(y.d), cout, 1 if bias else 0, x.d):
-        entry = 'es_dconv_fwd_bf16'
+        entry, gathered = 'es_dconv_fwd_bf16', True
     else:
         if maps is not None:
             nbr, inv = maps.get()
-        if bf and (x16 or (_ld(x.d) == cin and _use_shadow(n_in, cin, K, cin, cout))):
+        gathered = bool(bf and (x16 or (_ld(x.d) == cin and _use_shadow(n_in, cin, K, cin, cout))))    # the launch gathers x's bf16 shadow
+        if gathered:                               # (False: it reads the f32 rows)
             if (_halo_ok(nbr, n_out, n_in, cin, K, cin, cout)
-                    and _halo_launch(P(x.shadow()), cin, P(w.bf16()[1]), nbr, n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
-                                     cout, 0)):
+                    and _halo_launch(P(x.shadow()), cin, P(w.bf16()[1]), nbr, n_out, n_in, K, cin, cout, bias_p, P(y.d), cout, 0)):
                 entry = 'es_spconv_halo_bf16'
             else:
-                entry = _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
-                                  P(y.d), cout, 0, x.d)
+                entry = _fwd_bf16(P(x.shadow()), 1, cin, P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, bias_p, P(y.d), cout, 0, x.d)
         elif bf:
-            gathered = False
-            entry = _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0, P(y.d),
-                              cout, 0, x.d)
+            entry = _fwd_bf16(P(x.d), 0, _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, bias_p, P(y.d), cout, 0, x.d)
         else:
-            gathered = False
-            call('es_spconv_fwd', P(x.d), _ld(x.d), P(w.d), P(nbr), n_out, n_in, K, cin, cout, P(bias.d) if bias else 0,
-                 P(y.d), cout, 0, 0, _stream())
+            call('es_spconv_fwd', P(x.d), _ld(x.d), P(w.d), P(nbr), n_out, n_in, K, cin, cout, bias_p, P(y.d), cout, 0, 0, _stream())
             entry = 'es_spconv_fwd'
     if DEBUG_FWD is not None:
         if maps is not None:
@@ -797,6 +815,16 @@ def conv(x, w, nbr, inv, n_out, bias=None, need_dx=True, bias_from=0, dense=None
     y.fresh = True
     y.gsh = TAPE.enabled and bias is None and _grad_shadow_only(x, w, n_out, need_dx, bf)
     return y
+
+
+# The storage form of a convolution's output gradient: decided ONCE, by _conv_backward, and handed to _conv_wgrad / _conv_dgrad as a _Gy
+# (shadow: the bf16 matrix the gathering launches read -- SHADOWED, BF16 -- else None); an entry point's integers are made where it is called.
+F32, SHADOWED, BF16, PRE16 = 'f32 rows', 'f32 rows + cast shadow', 'bf16 rows of es_norm_bwd, their own shadow', 'pre-rounded bf16 rows of a join'
+_GY_F32 = (F32, SHADOWED)                          # the forms whose .rows are f32
+_Gy = namedtuple('_Gy', 'rows form shadow')
+# dy_half of es_spconv_wgrad_bf16_src for the matrix it is given (the shadow where there is one, else the rows)
+_DY_HALF = {F32: _C['ES_ROWS_F32'], SHADOWED: _C['ES_ROWS_BF16'], BF16: _C['ES_ROWS_BF16'], PRE16: _C['ES_ROWS_PRE16']}
+Img = namedtuple('Img', 'n_img H W stride')        # the image grid of a conv_affine layer; callers may pass a plain 4-tuple
 
 
 def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, gate=None, dense=None, maps=None, img=None, pre16=False):
@@ -819,40 +847,44 @@ def _conv_backward(x, w, nbr, inv, n_out, y, gy, bias, bias_from, need_dx, bf, g
         DEBUG_CONV.append(rec)
     # bf16 shadow of the output gradient: gather source of the data-gradient launch and, with the input's shadow from
     # the forward pass, of the weight-gradient launch (made here, before the weight-gradient stream forks)
-    gh = None
+    img = None if img is None else Img(*img)
+    g = _Gy(gy, F32, None)
     if gy.dtype == torch.bfloat16:               # bf16 gradient rows (GRAD_ROWS_BF16: nothing reads this gradient in f32) are their own
         assert bf and _ld(gy) == cout and bias is None              # shadow: no cast launch
         if pre16:
             assert K == 1 and x.d.dtype == torch.bfloat16
+            g = _Gy(gy, PRE16, None)
         else:                                    # from norm(): both launches gather the shadow anyway
             assert gy is y.g and _grad_shadow_only(x, w, n_out, need_dx, bf, gate)
-            gh = y.gh = gy
+            g = _Gy(gy, BF16, gy)
+            y.gh = gy
     elif dn_w is not None or dn_d is not None or _grad_shadow_only(x, w, n_out, need_dx, bf, gate, _ld(gy)):
-        gh = y.grad_shadow() if gy is y.g else _cast_rows(gy)
+        g = _Gy(gy, SHADOWED, y.grad_shadow() if gy is y.g else _cast_rows(gy))
     if dn_w is not None:
         x.shadow()                               # (made by the forward launch; never on the weight-gradient stream)
     if w.g is not None or (bias is not None and bias.g is not None):
-        sw = _wgrad_stream(gy, x.d, gh, x.dh)
+        sw = _wgrad_stream(gy, x.d, g.shadow, x.dh)
     if w.g is not None:
-        _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw, pre16)
+        _conv_wgrad(x, w, nbr, n_out, g, bf, dn_w, maps, img, sw)
     if bias is not None and bias.g is not None:
         # column sums of gy (round 4: one deterministic launch on the weight-gradient stream; was an f32 GEMM against a column of ones)
         nb, dst = cout - bias_from, bias.g.data_ptr() + 4 * bias_from
         ws, nf = stream_ws(sw, 'colsum', int(hip.raw('es_colsum_workspace_floats')(n_out, nb)), gy)
         call('es_colsum', gy.data_ptr() + 4 * bias_from, _ld(gy), n_out, nb, dst, _first_write(dst), P(ws), nf, sw)
     if need_dx and x.rg:
-        _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img, pre16)
+        _conv_dgrad(x, w, inv, n_out, g, bf, dn_d, maps, gate, img)
     if rec is not None and rec['need_dx']:
         rec['after'] = x.g.clone()               # (gradient buffer after this launch; `before` = what it accumulated onto)
 
 
-def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw, pre16=False):
+def _conv_wgrad(x, w, nbr, n_out, g, bf, dn_w, maps, img, sw):
     """the weight-gradient launch of a convolution on stream `sw`: the first candidate that takes it (a fast path's launcher has the
-    last word on the operands: -4 passes on to the next candidate)"""
+    last word on the operands: ES_DECLINED passes on to the next candidate).  g: the output gradient (_Gy)"""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
+    gy, gh = g.rows, g.shadow
     acc = _first_write(P(w.g))
-    xh_f32 = bf and x.dh is not None and gy.dtype == torch.float32      # bf16 activation rows against f32 gradient rows
+    xh_f32 = bf and x.dh is not None and g.form in _GY_F32              # bf16 activation rows against f32 gradient rows
     if dn_w is not None:                         # dense engine (dense_ok)
         if _dense_wgrad(P(x.dh), cin, P(gh), cout, dn_w, 0, cin, cout, P(w.g), acc, sw, gh):
             return
@@ -861,95 +893,93 @@ def _conv_wgrad(x, w, nbr, n_out, gy, gh, bf, dn_w, maps, img, sw, pre16=False):
             sw = _wgrad_stream()
     # 3x3 / pad 1 image layers, C -> C channels, by address arithmetic on the image grid (csrc/imgwgrad.hip)
     if IMG_WGRAD[0] and xh_f32 and img is not None and K == 9 and cin == cout:
-        nf = int(hip.raw('es_img_wgrad9_workspace_floats')(img[0], img[1], img[2], cin, img[3]))
+        nf = int(hip.raw('es_img_wgrad9_workspace_floats')(img.n_img, img.H, img.W, cin, img.stride))
         if nf:
             ws, nf = stream_ws(sw, 'wgrad', nf, gy)
-            if hip.try_call('es_img_wgrad9_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), img[0], img[1], img[2], cin, img[3], P(w.g), acc,
-                            P(ws), nf, sw):
+            if hip.try_call('es_img_wgrad9_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), img.n_img, img.H, img.W, cin, img.stride, P(w.g),
+                            acc, P(ws), nf, sw):
                 return
     # 1x1 layers on contiguous rows (identity map): streaming kernel (csrc/imgwgrad.hip)
-    if (xh_f32 or (pre16 and x.dh is not None)) and K == 1 and nbr is None and n_in == n_out:
+    if (xh_f32 or (g.form == PRE16 and x.dh is not None)) and K == 1 and nbr is None and n_in == n_out:
         nf = int(hip.raw('es_rows_wgrad1_workspace_floats')(n_out, cin, cout))
         if nf:
             ws, nf = stream_ws(sw, 'wgrad', nf, gy)
-            if hip.try_call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g), acc | (2 if pre16 else 0),
-                            P(ws), nf, sw):                      # (bit 1 of `accumulate`: bf16 gradient rows)
+            if hip.try_call('es_rows_wgrad1_bf16', P(x.dh), _ld(x.dh), P(gy), _ld(gy), n_out, cin, cout, P(w.g),
+                            acc | (_C['ES_ACC_ROWS_BF16'] if g.form == PRE16 else 0), P(ws), nf, sw):
                 return
     # map kernels: gathering from the bf16 shadows where they exist (bf16 activation rows are their own shadow)
     if bf and (gh is not None or x.dh is not None or x.d.dtype == torch.bfloat16):
         xs, ys = x.dh if x.dh is not None else x.d, gh if gh is not None else gy
-        # (dy_half 3: pre-rounded rows on the plan of the f32 matrix they stand for; 1: a shadow)
-        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), 3 if pre16 else int(gh is not None),
-               _ld(ys), P(nbr), n_out, n_in, K, cin, cout, like=gy, acc=acc)
+        _wgrad('es_spconv_wgrad_bf16_src', sw, P(w.g), P(xs), int(x.dh is not None), _ld(xs), P(ys), _DY_HALF[g.form], _ld(ys), P(nbr),
+               n_out, n_in, K, cin, cout, like=gy, acc=acc)
         return
     assert x.d.dtype == torch.float32, 'bf16 activation rows reach the weight gradient through their shadow (x.dh)'
     _wgrad('es_spconv_wgrad_bf16' if bf else 'es_spconv_wgrad', sw, P(w.g), P(x.d), _ld(x.d), P(gy), _ld(gy), P(nbr), n_out, n_in, K,
            cin, cout, like=gy, acc=acc)
 
 
-def _conv_dgrad(x, w, inv, n_out, gy, gh, bf, dn_d, maps, gate, img, pre16=False):
-    """the data-gradient launch of a convolution into x.g: the first candidate that takes it (as _conv_wgrad).  gate, pre16: see
-    _conv_backward"""
+def _conv_dgrad(x, w, inv, n_out, g, bf, dn_d, maps, gate, img):
+    """the data-gradient launch of a convolution into x.g: the first candidate that takes it (as _conv_wgrad).  gate: see _conv_backward;
+    g: the output gradient (_Gy)"""
     K, cin, cout = w.d.shape
     n_in = x.d.shape[0]
-    s = _stream()
+    gy, gh, s = g.rows, g.shadow, _stream()
+    x16 = x.d.dtype == torch.bfloat16
     if gate is not None:
         assert x.g is None and bf, 'gated dgrad: x must have exactly one consumer'
         x.g, x.gated = torch.empty(x.d.shape, dtype=torch.float32, device=x.d.device), True
-        # 3x3 image layer by address arithmetic (csrc/imgconv.hip, mode 1)
-        if (img is not None and K == 9 and img[3] == 1 and cin == cout and x.d.dtype == torch.bfloat16 and gy.dtype == torch.float32
-                and _ld(x.d) == cin and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, 1, 1) == 1
-                and hip.try_call('es_img_conv3_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, 1, 1, P(gate), 0, P(x.d),
-                                 _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)):
+        gated, wn = _C['ES_ACT_GATE'], P(w.bf16()[0])
+        im3 = img is not None and K == 9 and cin == cout and x16 and g.form in _GY_F32       # a 3x3 image layer (csrc/imgconv.hip)
+        # ... of stride 1 by address arithmetic (mode 1)
+        if (im3 and img.stride == 1 and _ld(x.d) == cin and hip.raw('es_img_conv3_supported')(img.n_img, img.H, img.W, cin, 1, 1) == 1
+                and hip.try_call('es_img_conv3_bf16', P(gy), _ld(gy), wn, img.n_img, img.H, img.W, cin, 1, 1, P(gate), 0, P(x.d), _ld(x.d),
+                                 gated, P(x.g), _C['ES_ROWS_F32'], _ld(x.g), s)):
             return
-        # 3x3 / stride-2 image layer: only the taps of each pixel's parity class (csrc/imgconv.hip, k_img_dgrad3_s2)
-        if (IMG_STRIDED_DGRAD[0] and img is not None and K == 9 and img[3] == 2 and cin == cout and x.d.dtype == torch.bfloat16
-                and gy.dtype == torch.float32 and hip.raw('es_img_dgrad3_s2_supported')(img[0], img[1], img[2], cin) == 1
-                and hip.try_call('es_img_dgrad3_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cin, P(gate), P(x.d),
-                                 _ld(x.d), P(x.g), _ld(x.g), s)):
+        # ... of stride 2: only the taps of each pixel's parity class (k_img_dgrad3_s2)
+        if (im3 and img.stride == 2 and IMG_STRIDED_DGRAD[0] and hip.raw('es_img_dgrad3_s2_supported')(img.n_img, img.H, img.W, cin) == 1
+                and hip.try_call('es_img_dgrad3_s2_bf16', P(gy), _ld(gy), wn, img.n_img, img.H, img.W, cin, P(gate), P(x.d), _ld(x.d),
+                                 P(x.g), _ld(x.g), s)):
             return
         if _is_mirror(inv):                      # the fused-epilogue entry points have no mirrored tap walk: the real inverse map
             inv = inv.real()
-        if x.d.dtype == torch.bfloat16:          # the gate operand is the bf16 activation (only its sign is read)
-            call('es_spconv_fwd_bf16_io', P(gy), int(gy.dtype == torch.bfloat16), _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin,
-                 P(gate), 0, P(x.d), 1, _ld(x.d), 3, P(x.g), 0, _ld(x.g), s)
+        if x16:                                  # the gate operand is the bf16 activation (only its sign is read); gy's rows as they are stored
+            call('es_spconv_fwd_bf16_io', P(gy), _C['ES_ROWS_F32' if g.form in _GY_F32 else 'ES_ROWS_BF16'], _ld(gy), wn, P(inv), n_in, n_out,
+                 K, cout, cin, P(gate), 0, P(x.d), _C['ES_ROWS_BF16'], _ld(x.d), gated, P(x.g), _C['ES_ROWS_F32'], _ld(x.g), s)
         else:
-            call('es_spconv_fwd_bf16_affine', P(gy), _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, P(gate), 0,
-                 P(x.d), _ld(x.d), 3, P(x.g), _ld(x.g), s)
+            call('es_spconv_fwd_bf16_affine', P(gy), _ld(gy), wn, P(inv), n_in, n_out, K, cout, cin, P(gate), 0, P(x.d), _ld(x.d), gated,
+                 P(x.g), _ld(x.g), s)
         return
-    g, acc = _grad_target(x, x.d)
+    dx, acc = _grad_target(x, x.d)
     # 1x1 / stride-2 image layer (downsample.0): a row GEMM over the gradient rows only, stored to the even pixels (k_img_dgrad1_s2)
-    if (IMG_STRIDED_DGRAD[0] and img is not None and K == 1 and img[3] == 2 and bf and gh is None and dn_d is None
-            and (gy.dtype == torch.float32 or pre16) and g.dtype == torch.float32 and n_in == img[0] * img[1] * img[2]
-            and hip.raw('es_img_dgrad1_s2_supported')(img[0], img[1], img[2], cout, cin) == 1
-            and hip.try_call('es_img_dgrad1_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img[0], img[1], img[2], cout, cin, P(g), _ld(g),
-                             acc | (2 if pre16 else 0), s)):         # (bit 1 of `accumulate`: bf16 gradient rows)
+    if (IMG_STRIDED_DGRAD[0] and img is not None and K == 1 and img.stride == 2 and bf and g.form in (F32, PRE16) and dn_d is None
+            and n_in == img.n_img * img.H * img.W and hip.raw('es_img_dgrad1_s2_supported')(img.n_img, img.H, img.W, cout, cin) == 1
+            and hip.try_call('es_img_dgrad1_s2_bf16', P(gy), _ld(gy), P(w.bf16()[0]), img.n_img, img.H, img.W, cout, cin, P(dx), _ld(dx),
+                             acc | (_C['ES_ACC_ROWS_BF16'] if g.form == PRE16 else 0), s)):
         return
     # pre-rounded rows reach an ungated data gradient only where that launch takes them (_pre16_ok, checked before they were chosen)
-    assert not pre16, 'pre-rounded gradient rows were chosen for a layer whose data gradient cannot take them'
+    assert g.form != PRE16, 'pre-rounded gradient rows were chosen for a layer whose data gradient cannot take them'
     if dn_d is not None:                         # dense engine (dense_ok)
-        if _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(g), _ld(g), acc, gh):
+        if _dense_launch(P(gh), cout, P(w.bf16()[0]), dn_d, 1, cin, cout, P(dx), _ld(dx), acc, gh):
             return
         if maps is not None:
             _, inv = maps.get()
     if gh is not None and _halo_ok(inv, n_in, n_out, cout, K, cout, cin) and \
-            _halo_launch(P(gh), cout, P(w.bf16()[0]), inv, n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc):
+            _halo_launch(P(gh), cout, P(w.bf16()[0]), inv, n_in, n_out, K, cout, cin, 0, P(dx), _ld(dx), acc):
         return
-    if _is_mirror(inv):                          # gather kernels on the forward map, taps mirrored (bit 1 of `accumulate`): same bits as on
-        inv, acc = inv.nbr, acc | 2              # the inverse map, which is never built
-    if gh is not None:
-        _fwd_bf16(P(gh), 1, cout, P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gh)
-    elif bf and cout >= 16:
-        _fwd_bf16(P(gy), 0, _ld(gy), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), acc, gy)
+    if _is_mirror(inv):                          # gather kernels on the forward map with the taps mirrored: same bits as on the inverse
+        inv, acc = inv.nbr, acc | _C['ES_ACC_MIRROR']                                                # map, which is never built
+    if gh is not None or (bf and cout >= 16):    # the gather reads the shadow where there is one (contiguous rows)
+        src, kind = (gy, _C['ES_ROWS_F32']) if gh is None else (gh, _C['ES_ROWS_BF16'])
+        _fwd_bf16(P(src), kind, _ld(src), P(w.bf16()[0]), P(inv), n_in, n_out, K, cout, cin, 0, P(dx), _ld(dx), acc, src)
     else:
-        call('es_spconv_fwd', P(gy), _ld(gy), P(w.d), P(inv), n_in, n_out, K, cout, cin, 0, P(g), _ld(g), 1, acc, s)
+        call('es_spconv_fwd', P(gy), _ld(gy), P(w.d), P(inv), n_in, n_out, K, cout, cin, 0, P(dx), _ld(dx), 1, acc, s)
 
 
 def _pre16_ok(x, w, nbr, n_in, n_out, need_dx, gate, img):
     """every backward launch of this K = 1 layer of the image backbone takes the gradient of its conv output as pre-rounded bf16 rows and
     gives the bits of the f32 rows (GRAD_ROWS_BF16).  The conditions imply the launchers' acceptance -- there is no way back to f32 rows once
     the join has written bf16: bf16 activation rows (never the small-linear weight-gradient plan, which reads f32), cout % 8 on fresh
-    contiguous rows (the alignment dy_half = 3 and the stride-2 kernel ask for), and a data gradient that is the gated K = 1 row GEMM, the
+    contiguous rows (the alignment ES_ROWS_PRE16 and the stride-2 kernel ask for), and a data gradient that is the gated K = 1 row GEMM, the
     stride-2 image kernel on a grid it supports, or absent."""
     K, cin, cout = w.d.shape
     if not (K == 1 and x.d.dtype == torch.bfloat16 and _ld(x.d) == cin and cout % 8 == 0):
@@ -958,8 +988,8 @@ def _pre16_ok(x, w, nbr, n_in, n_out, need_dx, gate, img):
         return True
     if gate is not None:
         return nbr is None and n_in == n_out
-    return bool(IMG_STRIDED_DGRAD[0] and img is not None and img[3] == 2 and n_in == img[0] * img[1] * img[2]
-                and hip.raw('es_img_dgrad1_s2_supported')(img[0], img[1], img[2], cout, cin) == 1)
+    return bool(IMG_STRIDED_DGRAD[0] and img is not None and img.stride == 2 and n_in == img.n_img * img.H * img.W
+                and hip.raw('es_img_dgrad1_s2_supported')(img.n_img, img.H, img.W, cout, cin) == 1)
 
 
 def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=True, sole_consumer=False, out_bf16=False, img=None,
@@ -977,24 +1007,25 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
     n_in = x.d.shape[0]
     if PRECISION[0] != 'bf16':
         return affine_act(conv(x, w, nbr, inv, n_out, need_dx=need_dx), scale, shift, act=act, res=res)
+    img = None if img is None else Img(*img)
     h16 = torch.bfloat16
     y16 = bool(out_bf16 and cout % 4 == 0)
     x16, r16 = x.d.dtype == h16, (res is not None and res.d.dtype == h16)
     y = Var(empty((n_out, cout), x.d, dtype=h16 if y16 else torch.float32))
+    res_p, ldr = (P(res.d), _ld(res.d)) if res is not None else (0, 0)
     # round 6: 3x3 layers on an image grid by address arithmetic (csrc/imgconv.hip) where the library takes the shape
     ic = (img is not None and K == 9 and x16 and res is None and act in (0, 1) and cin == cout and _ld(x.d) == cin
-          and hip.raw('es_img_conv3_supported')(img[0], img[1], img[2], cin, img[3], 0) == 1)
-    if ic and hip.try_call('es_img_conv3_bf16', P(x.d), cin, P(w.bf16()[1]), img[0], img[1], img[2], cin, img[3], 0, P(scale), P(shift), 0,
-                           0, act, P(y.d), int(y16), cout, _stream()):
-        entry = 'es_img_conv3_bf16'             # (-4: the launcher did not take the operands -- the map kernels below)
-    elif x16 or r16 or y16:
-        call('es_spconv_fwd_bf16_io', P(x.d), int(x16), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale),
-             P(shift), P(res.d) if res is not None else 0, int(r16), _ld(res.d) if res is not None else 0, act, P(y.d),
-             int(y16), cout, _stream())
+          and hip.raw('es_img_conv3_supported')(img.n_img, img.H, img.W, cin, img.stride, 0) == 1)
+    if ic and hip.try_call('es_img_conv3_bf16', P(x.d), cin, P(w.bf16()[1]), img.n_img, img.H, img.W, cin, img.stride, 0, P(scale), P(shift),
+                           0, 0, act, P(y.d), int(y16), cout, _stream()):
+        entry = 'es_img_conv3_bf16'             # (declined: the launcher did not take the operands -- the map kernels below)
+    elif x16 or r16 or y16:                     # (int(.16): ES_ROWS_F32 / ES_ROWS_BF16)
+        call('es_spconv_fwd_bf16_io', P(x.d), int(x16), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale), P(shift),
+             res_p, int(r16), ldr, act, P(y.d), int(y16), cout, _stream())
         entry = 'es_spconv_fwd_bf16_io'
     else:
-        call('es_spconv_fwd_bf16_affine', P(x.d), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale),
-             P(shift), P(res.d) if res is not None else 0, _ld(res.d) if res is not None else 0, act, P(y.d), cout, _stream())
+        call('es_spconv_fwd_bf16_affine', P(x.d), _ld(x.d), P(w.bf16()[1]), P(nbr), n_out, n_in, K, cin, cout, P(scale), P(shift), res_p,
+             ldr, act, P(y.d), cout, _stream())
         entry = 'es_spconv_fwd_bf16_affine'
     if y16:
         y.dh = y.d                              # bf16 rows are their own gather shadow
@@ -1031,10 +1062,7 @@ def conv_affine(x, w, nbr, inv, n_out, scale, shift, act=1, res=None, need_dx=Tr
                 res.g, res.gated = torch.empty((n_out, cout), dtype=h16, device=y.d.device), True
                 call('es_affine_act_bwd_yh_xh2', P(y.g), P(y.d), P(scale), P(res.fold), n_out, cout, act, P(gconv), P(res.g), _stream())
             else:
-                gr = accr = 0
-                if res is not None and res.rg:
-                    t, accr = _grad_target(res, res.d)
-                    gr = P(t)
+                gr, accr = _grad_ptr(res)
                 if rows16:
                     call('es_affine_act_bwd_yh_xh', P(y.g), P(y.d), P(scale), n_out, cout, act, P(gconv), gr, accr, _stream())
                 else:
@@ -1053,9 +1081,8 @@ def gen_conv_transpose(x, w):
     y = Var(empty((n * 8, cout), x.d))
     s = _stream()
     bf = PRECISION[0] == 'bf16'
-    fused = False
-    if bf and GEN_FUSED[0] and x.d.dtype == torch.float32:      # all eight taps in one launch
-        fused = hip.raw('es_gen_transpose_fwd_bf16')(P(x.d), _ld(x.d), P(w.bf16()[1]), n, cin, cout, P(y.d), s) == 0
+    fused = (bf and GEN_FUSED[0] and x.d.dtype == torch.float32      # all eight taps in one launch (declined: the per-tap launches)
+             and hip.try_call('es_gen_transpose_fwd_bf16', P(x.d), _ld(x.d), P(w.bf16()[1]), n, cin, cout, P(y.d), s))
     for k in range(0 if not fused else 8, 8):
         if bf:
             call('es_spconv_fwd_bf16', P(x.d), 0, _ld(x.d), w.bf16()[1].data_ptr() + 2 * k * cin * cout, 0, n, n, 1, cin,
@@ -1079,19 +1106,16 @@ def gen_conv_transpose(x, w):
             DEBUG_CONV.extend(recs)
         g, acc = _grad_target(x, x.d) if x.rg else (None, 0)
         sw = _wgrad_stream(y.g, x.d) if w.g is not None else s
-        dfused = False
-        if g is not None and bf and GEN_FUSED[0] and y.g.is_contiguous():      # (n * 8, cout) rows = (n, 8 cout)
-            dfused = hip.raw('es_gen_transpose_dgrad_bf16')(P(y.g), P(w.bf16()[0]), n, cin, cout, P(g), _ld(g), acc, s) == 0
+        dfused = (g is not None and bf and GEN_FUSED[0] and y.g.is_contiguous()      # (n * 8, cout) rows = (n, 8 cout)
+                  and hip.try_call('es_gen_transpose_dgrad_bf16', P(y.g), P(w.bf16()[0]), n, cin, cout, P(g), _ld(g), acc, s))
         wfused = False
         slots = [w.g.data_ptr() + 4 * k * cin * cout for k in range(8)] if w.g is not None else []
         if (w.g is not None and bf and GEN_FUSED[0] and HEAD_BWD_FUSED[0] and y.g.is_contiguous() and x.d.dtype == torch.float32
                 and len({_written(q) for q in slots}) == 1):        # all eight taps' weight gradients in one launch
             need = hip.raw('es_gen_transpose_wgrad_workspace_floats')(P(x.d), _ld(x.d), P(y.g), n, cin, cout)
             ws, nf = stream_ws(sw, 'wgrad', need, y.g) if need else (None, 0)
-            rc = hip.raw('es_gen_transpose_wgrad_bf16')(P(x.d), _ld(x.d), P(y.g), n, cin, cout, P(w.g), _written(slots[0]), P(ws), nf, sw)
-            if rc not in (0, 1):                                     # (1: shape not served, nothing launched -- the per-tap launches)
-                raise hip.HipError(f'es_gen_transpose_wgrad_bf16 failed with status {rc}')
-            wfused = rc == 0
+            wfused = hip.try_call('es_gen_transpose_wgrad_bf16', P(x.d), _ld(x.d), P(y.g), n, cin, cout, P(w.g), _written(slots[0]), P(ws),
+                                  nf, sw)                           # (declined: nothing launched -- the per-tap launches)
             if wfused:
                 for q in slots:
                     _first_write(q)
@@ -1193,22 +1217,19 @@ def norm(x, weight, bias, seg_off, eps, act=0, res=None, running=None, momentum=
         if GRAD_ROWS_BF16[0] and fuse and private and x.gsh and x.g is None and not _f32_grad_rows_wanted():
             # the producing convolution's backward gathers the shadow only: no f32 rows (GRAD_ROWS_BF16)
             x.g = gh = empty((n, C), x.d, dtype=torch.bfloat16)
-            call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
-                 P(weight.d), act, P(weight.g), P(bias.g), P(ws2), 0, C, 0, P(gh), s)
+            g, ldg, acc = None, C, 0
         else:
             g, acc = _grad_target(x, x.d)
-            gh = empty((n, C), x.d, dtype=torch.bfloat16) if (fuse and private and _ld(g) == C) else None
-            call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
-                 P(weight.d), act, P(weight.g), P(bias.g), P(ws2), P(g), _ld(g), acc, P(gh), s)
+            ldg = _ld(g)
+            gh = empty((n, C), x.d, dtype=torch.bfloat16) if (fuse and private and ldg == C) else None
+        call('es_norm_bwd', P(y.g), _ld(y.g), P(y.d), C, P(x.d), _ld(x.d), n, C, so, nseg, P(mean), P(invstd),
+             P(weight.d), act, P(weight.g), P(bias.g), P(ws2), P(g), ldg, acc, P(gh), s)
         x.gh = gh
         if DEBUG_GRADS is not None:
             DEBUG_GRADS[('norm', id(y))] = dict(dx=g.clone(), dz=y.g.clone(), mean=mean.clone(), invstd=invstd.clone(),
                                                 x=x.d.clone(), yd=y.d.clone(), acc=acc, n=n, C=C, act=act)
         if res is not None and res.rg:          # y.g now holds dz == gradient of the residual input
-            if res.g is None:
-                res.g = y.g
-            else:
-                call('es_axpy2d', P(res.g), _ld(res.g), P(y.g), _ld(y.g), n, C, 1.0, 1, s)
+            _grad_give(res, y.g)
     TAPE.add(bwd)
     return y
 
@@ -1226,13 +1247,7 @@ def affine_act(x, scale, shift, act=1, res=None, need_dx=True):
     def bwd():
         if y.g is None:
             return
-        gx = accx = gr = accr = 0
-        if need_dx and x.rg:
-            t, accx = _grad_target(x, x.d)
-            gx = P(t)
-        if res is not None and res.rg:
-            t, accr = _grad_target(res, res.d)
-            gr = P(t)
+        (gx, accx), (gr, accr) = _grad_ptr(x if need_dx else None), _grad_ptr(res)
         if gx or gr:
             call('es_affine_act_bwd', P(y.g), P(y.d), P(scale), n, C, act, gx, accx, gr, accr, _stream())
     TAPE.add(bwd)
@@ -1321,14 +1336,8 @@ def concat_rows(vs):
         if y.g is None:
             return
         for i, v in enumerate(vs):
-            if not v.rg:
-                continue
-            part = y.g[offs[i]:offs[i + 1]]
-            if v.g is None:
-                v.g = part
-            else:
-                call('es_axpy2d', P(v.g), _ld(v.g), P(part), _ld(y.g), part.shape[0], part.shape[1], 1.0, 1, _stream())
-            v.gh = None
+            if v.rg:
+                _grad_give(v, y.g[offs[i]:offs[i + 1]])
     TAPE.add(bwd)
     return y
 
@@ -1349,13 +1358,9 @@ def union_add(a, b, pos_a, pos_b, n):
             if not v.rg:
                 continue
             m = v.d.shape[0]
-            if v.g is None:
-                v.g = empty((m, C), a.d)
-                call('es_row_move', P(v.g), C, P(y.g), _ld(y.g), P(pos), m, C, 0, s)
-            else:
-                t = empty((m, C), a.d)
-                call('es_row_move', P(t), C, P(y.g), _ld(y.g), P(pos), m, C, 0, s)
-                call('es_axpy2d', P(v.g), _ld(v.g), P(t), C, m, C, 1.0, 1, s)
+            t = empty((m, C), a.d)
+            call('es_row_move', P(t), C, P(y.g), _ld(y.g), P(pos), m, C, 0, s)
+            _grad_give(v, t)
     TAPE.add(bwd)
     return y
 
@@ -1383,12 +1388,8 @@ def add(a, b):
         if y.g is None:
             return
         for v in (a, b):
-            if not v.rg:
-                continue
-            if v.g is None:
-                v.g = y.g if v is a and not b.rg else y.g.clone()
-            else:
-                call('es_axpy2d', P(v.g), _ld(v.g), P(y.g), _ld(y.g), n, C, 1.0, 1, _stream())
+            if v.rg:
+                _grad_give(v, y.g, alias=v is a and not b.rg)         # (y.g serves one input at most: later consumers add into theirs)
     TAPE.add(bwd)
     return y
 
@@ -1471,11 +1472,7 @@ def layernorm(x, w, b, res=None, eps=1e-5):
             rec.update(dz=dz.clone(), dw1=w.g.clone(), db1=b.g.clone())
         owned = False                            # dz may be handed to exactly one input as its gradient buffer
         for v in tgt:
-            if v.g is None:
-                v.g = dz if not owned else dz.clone()
-                owned = True
-            else:
-                call('es_axpy2d', P(v.g), _ld(v.g), P(dz), C, n, C, 1.0, 1, s)
+            owned |= _grad_give(v, dz, alias=not owned)
     TAPE.add(bwd)
     return y
 
@@ -1520,7 +1517,7 @@ def attention(q, k, v, B, H, Lq, Lk, klen=None):
 # ---- one scene, many prompts: forward only for SparseFeatureFusion3DGrounder.ground (nothing on the tape), taped for loss_shared
 # backward of the taped attention_kv: es_attn_kv_bwd (the query side converted once per call, the workgroup's key tile resident) or
 # es_attn_bwd with B = 1 -- the same function (A/B switch; the default follows the decision in DESIGN section 3c, tools/bench_shared_train.py)
-ATTN_KV_BWD = [os.environ.get('ES_ATTN_KV_BWD', '1') != '0']
+ATTN_KV_BWD = _switch('ES_ATTN_KV_BWD')
 
 
 class PreparedKV:

@@ -38,7 +38,7 @@ def parse_header(path=HEADER_PATH):
 
 
 PROTOS = parse_header()
-CONSTS = {k: int(v) for k, v in re.findall(r'#define\s+(ES_\w+)\s+(\d+)', open(HEADER_PATH).read())}
+CONSTS = {k: int(v) for k, v in re.findall(r'#define\s+(ES_\w+)\s+(-?\d+)', open(HEADER_PATH).read())}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f'{LIB_PATH} is missing: build it with `make -C embodiedscan_amd/csrc` '
@@ -51,16 +51,13 @@ for _name, (_ret, _at, _an) in PROTOS.items():
     _fn[_name] = _f
 
 
-if os.environ.get('ES_PINGPONG') is not None:          # A/B switch of the ping-pong LDS conv kernels (default: on)
-    _fn['es_set_option'](1, int(os.environ['ES_PINGPONG']))
-if os.environ.get('ES_WGRAD_HUGE') is not None:        # A/B switch of the 256x256 weight-gradient tile (default: on)
-    _fn['es_set_option'](2, int(os.environ['ES_WGRAD_HUGE']))
-if os.environ.get('ES_ROWGEMM') is not None:           # A/B switch of the K = 1 streaming row-GEMM kernel (default: on)
-    _fn['es_set_option'](3, int(os.environ['ES_ROWGEMM']))
-# tuning sweeps without a rebuild (tools/gpu_sweep.sh): weight-gradient slice targets, workspace cap, forward tap-split threshold
-for _key, _env in ((4, 'ES_WG_BIG_TARGET'), (5, 'ES_WG_BIG_ROWS'), (6, 'ES_WG_SMALL_TARGET'), (7, 'ES_WG_CAP_MB'), (8, 'ES_FWD_SPLIT_WGS'),
-                  (10, 'ES_DMA'), (11, 'ES_DMA_MIN_CIN'), (12, 'ES_RG128_MIN_CIN'), (14, 'ES_WGRAD_TR'), (15, 'ES_NORM_CB_ROWS'),
-                  (16, 'ES_SPLIT_FOLD'), (19, 'ES_RG128_MIN_WGS'), (20, 'ES_WSHARE'), (21, 'ES_NARROW'), (23, 'ES_RG320'), (24, 'ES_LIN_SMALL'), (25, 'ES_EXPAND'), (26, 'ES_EXPAND_WGS')):
+# es_set_option keys from the environment.  A/B switches (default: on): 1 the ping-pong LDS conv kernels, 2 the 256x256 weight-gradient tile,
+# 3 the K = 1 streaming row-GEMM kernel; then tuning sweeps without a rebuild (tools/gpu_sweep.sh): weight-gradient slice targets, workspace cap,
+# forward tap-split threshold ...
+for _key, _env in ((1, 'ES_PINGPONG'), (2, 'ES_WGRAD_HUGE'), (3, 'ES_ROWGEMM'), (4, 'ES_WG_BIG_TARGET'), (5, 'ES_WG_BIG_ROWS'), (6, 'ES_WG_SMALL_TARGET'),
+                   (7, 'ES_WG_CAP_MB'), (8, 'ES_FWD_SPLIT_WGS'), (10, 'ES_DMA'), (11, 'ES_DMA_MIN_CIN'), (12, 'ES_RG128_MIN_CIN'), (14, 'ES_WGRAD_TR'),
+                   (15, 'ES_NORM_CB_ROWS'), (16, 'ES_SPLIT_FOLD'), (19, 'ES_RG128_MIN_WGS'), (20, 'ES_WSHARE'), (21, 'ES_NARROW'), (23, 'ES_RG320'),
+                   (24, 'ES_LIN_SMALL'), (25, 'ES_EXPAND'), (26, 'ES_EXPAND_WGS')):
     if os.environ.get(_env) is not None:
         _fn['es_set_option'](_key, int(os.environ[_env]))
 if os.environ.get('ES_FOCAL_INFLIGHT') is not None:    # A/B switch of the focal-loss kernel with its loads in flight (default: on)
@@ -116,15 +113,18 @@ def call(name, *args):
 
 
 def try_call(name, *args):
-    """call() for a fast path whose launcher has the last word on its operands (leading dimensions, alignment, 32-bit row indices):
-    False when it returns -4 -- nothing was launched, the caller takes its next candidate"""
+    """call() for a fast path whose launcher has the last word on its operands (leading dimensions, alignment, 32-bit row indices): False when
+    it returns its "declined" status (ES_DECLINED; the es_gen_transpose_* launches: ES_GEN_DECLINED) -- nothing was launched, the caller
+    takes its next candidate"""
     rc = _launch(name, args)
-    if rc not in (0, -4):
+    if rc not in (0, CONSTS['ES_GEN_DECLINED' if name.startswith('es_gen_transpose_') else 'ES_DECLINED']):
         raise HipError(f'{name} failed with status {rc}')
     return rc == 0
 
 
 def raw(name):
+    """the bare ctypes function, for host queries only (*_workspace_*, *_supported, *_is_fast, *_bytes, *_rows, *_set_option): what queues work goes
+    through call() / try_call(), which check the status and are what PROFILE and the tests' launch recorders see"""
     return _fn[name]
 
 

@@ -111,10 +111,16 @@ int es_compact_mask(const int64_t* keys, int n, const int* mask, int* scratch, i
 /* Y[j] (+)= sum_k X[nbr[j,k]] . W[k] (+ bias).  W is [K][Cin][Cout]; trans_w: W is [K][Cout][Cin] (dgrad).
  * nbr == NULL means the identity map with K == 1 (plain row GEMM).  mink_resnet.py:58-62,88-120;
  * fcaf3d_head.py:907-984,1116-1136
- * `accumulate` of es_spconv_fwd, es_spconv_fwd_bf16 and es_spconv_fwd_bf16_ws is a bit set: bit 0 = add to Y, bit 1 = MIRRORED TAP WALK:
+ * `accumulate` of es_spconv_fwd, es_spconv_fwd_bf16 and es_spconv_fwd_bf16_ws is a bit set: bit 0 (ES_ACC_ADD) = add to Y, bit 1 (ES_ACC_MIRROR) = MIRRORED TAP WALK:
  * tap k of row j gathers X[nbr[j, K - 1 - k]].  A coordinate set's own odd-kernel map read this way IS its inverse map
  * (inv[i][k] == nbr[i][K - 1 - k]), so a stride-1 data gradient runs on the forward map and no inverse map is built; only the staging of
  * the map tile differs, the output bits equal a launch on the real inverse map.  -3: bit 1 with an even K or nbr == NULL. */
+#define ES_ACC_ADD 1      /* `accumulate` bit 0, every entry point that has the argument: add to the output instead of overwriting it */
+#define ES_ACC_MIRROR 2   /* `accumulate` bit 1 of es_spconv_fwd / es_spconv_fwd_bf16 / es_spconv_fwd_bf16_ws ONLY: mirrored tap walk */
+/* Status of a fast path whose launcher does not take the operands it was given: nothing was launched, nothing written, the caller
+ * takes its next candidate.  Every other non-zero status is an error. */
+#define ES_DECLINED -4     /* every entry point but the three below */
+#define ES_GEN_DECLINED 1  /* es_gen_transpose_fwd_bf16 / es_gen_transpose_dgrad_bf16 / es_gen_transpose_wgrad_bf16 */
 int es_spconv_fwd(const float* X, int ldx, const float* W, const int* nbr, int n_out, int n_in, int K, int Cin,
                   int Cout, const float* bias, float* Y, int ldy, int trans_w, int accumulate, void* stream);
 /* bf16-MFMA variant (f32 features rounded to bf16 while staged, f32 accumulate).  W_bf16 is [K][Cout][Cin]
@@ -178,12 +184,19 @@ int es_set_option(int key, int value);
  * 2 ELU (expf(z) - 1 below 0, as es_affine_act_fwd),
  * 3 "gate": Y = (res > 0) ? (X*W) * scale[c] : 0 -- the data-gradient conv of layer i+1 fused with the ReLU / frozen-BN
  * backward of layer i (res = layer i's output, scale = its folded BN scale; shift may be NULL). */
+#define ES_ACT_NONE 0 /* `act` of the fused epilogues, the norms and es_affine_act_*: the affine value itself */
+#define ES_ACT_RELU 1 /* max(z, 0) */
+#define ES_ACT_ELU 2  /* z below 0 -> expf(z) - 1; not taken by the bf16-output and image-grid entry points (their comments) */
+#define ES_ACT_GATE 3 /* es_spconv_fwd_bf16_affine / es_spconv_fwd_bf16_io / es_img_conv3_bf16 (mode 1) only: the gated data gradient above */
 int es_spconv_fwd_bf16_affine(const void* X, int ldx, const void* W_bf16, const int* nbr, int n_out, int n_in, int K,
                               int Cin, int Cout, const float* scale, const float* shift, const float* res, int ldr,
                               int act, float* Y, int ldy, void* stream);
 /* Fused conv + frozen-BN (+ residual) (+ ReLU) / gated data gradient with per-operand storage kinds (round 3: the image
  * backbone keeps its ACTIVATIONS in bf16): x_half / res_half / y_half non-zero -> that row matrix is bf16 (ld in elements).
  * Replaces conv -> BatchNorm2d(eval) -> (+ identity) -> ReLU of mmdet.ResNet Bottleneck (configs/detection/...py:24-34). */
+#define ES_ROWS_F32 0   /* storage kind of a row matrix (x_half / res_half / y_half / dy_half / x_is_bf16): f32 rows */
+#define ES_ROWS_BF16 1  /* bf16 rows (activations kept in bf16, or the es_cast_rows_bf16 shadow of an f32 matrix); ld in elements */
+#define ES_ROWS_PRE16 3 /* dy_half of es_spconv_wgrad_bf16_src ONLY: pre-rounded bf16 rows on the plan of the f32 matrix they stand for */
 int es_spconv_fwd_bf16_io(const void* X, int x_half, int ldx, const void* W_bf16, const int* nbr, int n_out, int n_in, int K,
                           int Cin, int Cout, const float* scale, const float* shift, const void* res, int res_half, int ldr,
                           int act, void* Y, int y_half, int ldy, void* stream);
@@ -229,7 +242,7 @@ int es_spconv_wgrad_bf16(const float* X, int ldx, const float* dY, int ldy, cons
  * dy_half non-zero -> X / dY point at (n, ld) bf16 rows (ld in elements).  Results are bit-identical to
  * es_spconv_wgrad_bf16 on the f32 originals when both launches use the same tile and slices (the f32 path rounds to the
  * same bf16 values while staging); the gathered bytes halve.
- * dy_half = 3: dY holds the PRE-ROUNDED bf16 rows of an f32 gradient matrix that was never stored (es_affine_act_bwd_yh_xh): tile, slices
+ * dy_half = 3 (ES_ROWS_PRE16): dY holds the PRE-ROUNDED bf16 rows of an f32 gradient matrix that was never stored (es_affine_act_bwd_yh_xh): tile, slices
  * and kernel family are those of dy_half = 0 on that f32 matrix with the same ldy, so the result is that launch's bit for bit (dy_half = 1
  * may pick the tiles only a pair of shadows can feed).  ldy % 8 != 0, dY not 16-byte aligned or the small-linear plan: -4, nothing written. */
 int es_spconv_wgrad_bf16_src(const void* X, int x_half, int ldx, const void* dY, int dy_half, int ldy, const int* nbr,
@@ -795,8 +808,10 @@ int es_img_wgrad_set_option(int key, int value);
  * of 64 up to 512, or 32 against >= 64; taken from 256 input channels or from 500 000 rows (es_img_wgrad_set_option 43), where it beats
  * the ring kernel.  es_rows_wgrad1_workspace_floats returns 0 for a shape it does not take (the caller keeps
  * es_spconv_wgrad_bf16_src); -4 / -5 as above.  Partial tensors per row slice, added in slice order: bit-reproducible.
- * Bit 1 of `accumulate` (value 2): dY points at bf16 rows (ldy in elements) holding the pre-rounded values of that f32 matrix
+ * Bit 1 of `accumulate` (ES_ACC_ROWS_BF16): dY points at bf16 rows (ldy in elements) holding the pre-rounded values of that f32 matrix
  * (es_affine_act_bwd_yh_xh) -- same tiles, slices and summation order, the f32 form's result bit for bit. */
+#define ES_ACC_ROWS_BF16 2 /* `accumulate` bit 1 of es_rows_wgrad1_bf16 / es_img_dgrad1_s2_bf16 ONLY: the gradient rows are pre-rounded bf16
+                            * (the value of ES_ACC_MIRROR, another meaning: the conv forward family reads this bit as the mirrored tap walk) */
 size_t es_rows_wgrad1_workspace_floats(int n, int Cin, int Cout);
 int es_rows_wgrad1_bf16(const void* Xh, int ldx, const float* dY, int ldy, int n, int Cin, int Cout, float* dW, int accumulate, float* ws,
                         size_t ws_floats, void* stream);
@@ -827,7 +842,7 @@ int es_img_conv_set_option(int key, int value);
  * es_img_dgrad1_s2_bf16: data gradient of a 1x1 / stride-2 layer -- es_spconv_fwd_bf16 on the 1-wide inverse map:
  *   dX[(im, 2 oy, 2 ox)] (+)= G[(im, oy, ox)] . W^T, G (x ldg) f32 rows of Cg channels, W_bf16 = the natural [Cx][Cg] copy, dX (x ldx) f32 rows
  *   of Cx channels; Cg, Cx multiples of 32.  accumulate 0: the same launch stores zeros to the three other pixels of every 2x2 cell;
- *   accumulate 1: they are not touched.  Bit 1 of `accumulate` (value 2): G points at bf16 rows (ldg in elements, a multiple of 8) holding
+ *   accumulate 1: they are not touched.  Bit 1 of `accumulate` (ES_ACC_ROWS_BF16): G points at bf16 rows (ldg in elements, a multiple of 8) holding
  *   the pre-rounded values of that f32 matrix (es_affine_act_bwd_yh_xh) -- same tiles, chunks and sums, the f32 form's result bit for bit.
  * The _supported queries answer for fresh contiguous operands; the launchers apply the same check (even H / W, leading dimensions multiples
  * of 4, 16-byte aligned pointers, rows x ld < 2^31) to the operands they are given and return -4, writing nothing, where it fails.
