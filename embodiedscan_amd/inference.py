@@ -2,7 +2,7 @@
 the model consumed: the reference's demo (demo/demo.py) without the 3-D viewer.
 
     python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json] [--render DIR]
-                                         [--track [--track-iou X] [--track-max-age K]]
+                                         [--map DIR [--map-cell M] [--map-z ZMIN ZMAX]] [--track [--track-iou X] [--track-max-age K]]
 
 reads D/S/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}, runs the model of CONFIG in
 `predict` mode (or frame by frame through a walk session with --walk) and writes the filtered boxes, scores, labels and class names
@@ -17,6 +17,13 @@ compared in f32, like the score, against the f32 value of the threshold; a NaN I
 render=DIR (run_scene, walk_scene, --render): frame_0000.png ... = dscan['img'] -- the resized frames the image backbone saw -- under the
 prediction, projected with that sample's own depth2img matrices (frame_matrices), so the picture shows the projection the fusion used;
 legend.json (class name -> colour) lies next to them.  embodiedscan_amd.render draws on the device; with render=None nothing of it runs.
+
+map=DIR (run_scene, walk_scene, --map [--map-cell M] [--map-z ZMIN ZMAX]): the scene seen from above (embodiedscan_amd.scene_map, DESIGN
+3i).  run_scene writes DIR/map.png -- every view's depth pixels in the frames' colours, z-buffered from above under the z cut, under the final
+boxes' footprints (or the final volume's top surface) and the trail of the camera centres --, DIR/map.json (the grid, the z cut and
+max_depth: a pixel maps back to metres) and DIR/legend.json; walk_scene writes map_0000.png ...: map t holds frames 0 .. t, the prediction of
+prefix t and the trail so far.  The grid is fixed before the first frame: the rectangle of all camera centres grown by 8 m (detectors) or the
+xy rectangle of point_cloud_range (occupancy).  With map=None nothing of it runs.
 
 --track (with --walk, the cont-det3d model; walk_scene(track=dict(...))): a tracks.TrackTable is updated with every frame's filtered list,
 the records gain track_ids -- the same object keeps its id from frame to frame -- and --render colours by track (legend.json: track_<id> ->
@@ -41,6 +48,7 @@ import torch
 from . import hip
 from . import pipeline as PL
 from . import render as RD
+from . import scene_map as SM
 from .structures import EulerDepthInstance3DBoxes, InstanceData
 
 MAX_ROWS, MAX_CLASSES = 16384, 4096          # limits of es_topk_sorted / es_box3d_iou_filter
@@ -253,11 +261,10 @@ def make_scene_batch(detector, dscan):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the picture
-def frame_matrices(dscan):
-    """-> (extrinsic, intrinsic), (V, 4, 4) f64 each: the scan's depth2img matrices at the resolution of dscan['img'] -- the fusion projects
-    with intrinsic @ extrinsic and then applies the resize's scale_factor (point_fusion.py:79-105); here the factor is folded into the
-    intrinsic's first two rows.  ValueError for a scan whose pipeline flipped / cropped the image or moved the cloud (a train-time
-    augmentation: its predictions do not live in the aligned frame)."""
+def _scan_matrices(dscan):
+    """-> (extrinsic, intrinsic, (sx, sy)): the scan's depth2img matrices, (V, 4, 4) f64 each, as the meta carries them, and the resize's
+    scale_factor.  ValueError for a scan whose pipeline flipped / cropped the image or moved the cloud (a train-time augmentation: its
+    predictions do not live in the aligned frame)."""
     meta = dscan['meta']
     pm = meta[PL.projection_key(meta)]
     E = np.stack([np.asarray(e, np.float64) for e in pm['extrinsic']])
@@ -269,9 +276,24 @@ def frame_matrices(dscan):
     if moved or meta.get('flip', False) or tuple(meta.get('img_crop_offset', (0., 0.))) != (0., 0.):
         raise ValueError('render: the pipeline augments the scan; draw on a test pipeline')
     sx, sy = (float(s) for s in meta.get('scale_factor', (1., 1.)))
-    K = K.copy()
+    return E, K.copy(), (sx, sy)
+
+
+def frame_matrices(dscan):
+    """-> (extrinsic, intrinsic), (V, 4, 4) f64 each: the scan's depth2img matrices at the resolution of dscan['img'] -- the fusion projects
+    with intrinsic @ extrinsic and then applies the resize's scale_factor (point_fusion.py:79-105); here the factor is folded into the
+    intrinsic's first two rows.  ValueError for a scan whose pipeline flipped / cropped the image or moved the cloud (a train-time
+    augmentation: its predictions do not live in the aligned frame)."""
+    E, K, (sx, sy) = _scan_matrices(dscan)
     K[:, 0, :] *= sx
     K[:, 1, :] *= sy
+    return E, K
+
+
+def depth_matrices(dscan):
+    """-> (extrinsic, intrinsic), (V, 4, 4) f64 each, at the resolution of dscan['depth']: frame_matrices without the scale_factor (the
+    depth maps are never resized), with the same refusal of an augmenting pipeline"""
+    E, K, _ = _scan_matrices(dscan)
     return E, K
 
 
@@ -327,11 +349,13 @@ def _filtered(detector, inst, filter):
     return filter_instances(inst, **dict(dict(n_classes=detector.bbox_head.num_classes), **filter))
 
 
-def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None, class_names=None):
+def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None, class_names=None, map=None, map_cell=0.02, map_z=(-1.0, 2.0)):
     """one `predict` over the folder.  Detectors: the filtered InstanceData per sample (the cont-det3d detector: one per prefix);
     occupancy models: pred_occupancy per sample / prefix.  filter: keyword arguments of filter_instances; None: the raw prediction.
     render: a directory that receives every view of the scan under the final list / volume (the last prefix's for the continuous kinds)
-    as frame_0000.png ... and legend.json; None: nothing is drawn."""
+    as frame_0000.png ... and legend.json; None: nothing is drawn.
+    map: a directory that receives map.png, map.json and legend.json -- the whole recording seen from above under that same final
+    prediction, in cells of map_cell metres, showing z in [map_z[0], map_z[1]); None: nothing of it runs."""
     kind = _kind(detector)
     dscan = load_scene(detector, scene_dir, pipeline, seed)
     data = detector.data_preprocessor(make_scene_batch(detector, dscan), False)
@@ -342,6 +366,8 @@ def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None,
         res = [_filtered(detector, ds.pred_instances_3d, filter) for ds in out]
     if render is not None:
         _prediction_painter(render, detector, class_names, dscan)(res[-1])
+    if map is not None:
+        _map_painter(map, detector, class_names, dscan, map_cell, map_z)(res[-1])
     return res
 
 
@@ -366,19 +392,15 @@ def _scene_walk(detector, dscan, batch, max_frames, capped):
     return walk, n_frames, frames()
 
 
-def _track_painter(dir, detector, class_names, dscan, table):
-    """the painter of a tracked walk: a box takes the colour of its track, render.class_palette(257)[1:][id % 256], so two chairs differ
-    and one chair keeps its colour when its arg-max label flickers; legend.json maps track_<id> -> {color, class_name} for every track
-    drawn so far (the class of the track's best detection) and is rewritten after every frame"""
-    names, _ = _class_legend(detector, class_names)
-    pal = RD.class_palette(257)[1:]
-    paint = _painter(dir, [], pal, dscan, detector.device,
-                     lambda frames, E, K, res, pal_dev: RD.render_boxes(frames, E, K, res.bboxes_3d, pal_dev[res.track_ids.remainder(256)].contiguous(),
-                                                                        layout='chw'))
+TRACK_PALETTE = 257                      # a track takes render.class_palette(257)[1:][id % 256]
+
+
+def _track_legend(dir, names, pal, table):
+    """-> update(res): legend.json of a tracked walk, track_<id> -> {color, class_name} for every track drawn so far (the class of the track's
+    best detection), rewritten after every frame"""
     legend = {}
 
-    def paint_tracks(res, t=None):
-        paint(res, t)
+    def update(res):
         ids = res.track_ids.cpu().tolist()
         labels = table.i[res.track_ids.clamp(min=0), 0].cpu().tolist()
         for i, l in zip(ids, labels):
@@ -386,16 +408,82 @@ def _track_painter(dir, detector, class_names, dscan, table):
                 legend[f'track_{i}'] = dict(color=[int(c) for c in pal[i % 256]], class_name=names[l] if 0 <= l < len(names) else f'class_{l}')
         with open(os.path.join(dir, 'legend.json'), 'w') as f:
             json.dump(legend, f)
+    return update
+
+
+def _track_painter(dir, detector, class_names, dscan, table):
+    """the painter of a tracked walk: a box takes the colour of its track, render.class_palette(257)[1:][id % 256], so two chairs differ
+    and one chair keeps its colour when its arg-max label flickers; legend.json maps track_<id> -> {color, class_name} for every track
+    drawn so far (the class of the track's best detection) and is rewritten after every frame"""
+    names, _ = _class_legend(detector, class_names)
+    pal = RD.class_palette(TRACK_PALETTE)[1:]
+    paint = _painter(dir, [], pal, dscan, detector.device,
+                     lambda frames, E, K, res, pal_dev: RD.render_boxes(frames, E, K, res.bboxes_3d, pal_dev[res.track_ids.remainder(256)].contiguous(),
+                                                                        layout='chw'))
+    legend = _track_legend(dir, names, pal, table)
+
+    def paint_tracks(res, t=None):
+        paint(res, t)
+        legend(res)
     return paint_tracks
 
 
-def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None, track=None):
+def _map_painter(dir, detector, class_names, dscan, cell, z, table=None, max_depth=8.0):
+    """fixes the grid from ALL of the scan's poses (occupancy kinds: from point_cloud_range), writes dir/map.json and dir/legend.json now
+    -> paint(res, t=None): t None: every view is splatted and map.png holds the prediction `res` and the whole trail; else frame t joins
+    the map and map_<t>.png holds the prediction of prefix t and the trail so far.  table: the boxes take their track's colour."""
+    os.makedirs(dir, exist_ok=True)
+    kind, dev = _kind(detector), detector.device
+    E, K = depth_matrices(dscan)
+    centres = RD.camera_rays(E, K)[:, 9:]
+    z_min, z_max = (float(v) for v in z)
+    if kind in ('occ', 'cont-occ'):
+        pr = np.asarray(detector.point_cloud_range, np.float64)
+        grid = SM.MapGrid.covering(pr[:2], pr[3:5], cell, z_min, z_max)
+    else:
+        grid = SM.MapGrid.around(centres, cell=cell, z_min=z_min, z_max=z_max)
+    smap = SM.SceneMap(grid, dev, max_depth)
+    with open(os.path.join(dir, 'map.json'), 'w') as f:
+        json.dump(dict(grid=grid.to_json(), max_depth=smap.max_depth, trail_color=list(SM.TRAIL_COLOR)), f)
+    names, pal = _class_legend(detector, class_names)
+    track_legend = None
+    if table is None:
+        with open(os.path.join(dir, 'legend.json'), 'w') as f:
+            json.dump({nm: [int(c) for c in pal[i]] for i, nm in enumerate(names)}, f)
+    else:
+        pal = RD.class_palette(TRACK_PALETTE)[1:]
+        track_legend = _track_legend(dir, names, pal, table)
+    pal_dev = torch.from_numpy(pal).to(dev)
+
+    def paint(res, t=None):
+        v = slice(None) if t is None else slice(t, t + 1)
+        smap.add(dscan['depth'][v], dscan['img'][v], E[v], K[v], layout='chw')
+        img = smap.image()
+        if not isinstance(res, InstanceData):
+            smap.draw_occupancy(img, res, detector.point_cloud_range, pal_dev)
+        elif table is not None:
+            smap.draw_boxes(img, res.bboxes_3d, pal_dev[res.track_ids.remainder(256)].contiguous())
+        else:
+            smap.draw_boxes(img, res.bboxes_3d, pal_dev[res.labels_3d.long().clamp(0, pal_dev.shape[0] - 1)])
+        smap.draw_trail(img, centres if t is None else centres[:t + 1])
+        path = RD.save_frames(dir, img[None], stem='map', start=t or 0)[0]
+        if t is None:
+            os.replace(path, os.path.join(dir, 'map.png'))
+        if track_legend is not None:
+            track_legend(res)
+    return paint
+
+
+def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None, track=None, map=None,
+               map_cell=0.02, map_z=(-1.0, 2.0)):
     """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene): opens a walk
     session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy).  render: a directory that receives
     frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn.
     track (cont-det3d): keyword arguments of tracks.TrackTable (dict(): its defaults).  The table is updated with the filtered list of
     every frame, and the yielded InstanceData gain track_ids (int64; -1: the table was full), track_hits and track_first_seen, all on the
-    device; with render the boxes take their track's colour (_track_painter).  None: no table, nothing of it runs."""
+    device; with render the boxes take their track's colour (_track_painter).  None: no table, nothing of it runs.
+    map: a directory that receives map_<t>.png -- frames 0 .. t seen from above under the prediction of prefix t and the trail so far, on
+    a grid fixed before the first frame from all of the folder's poses --, map.json and legend.json (run_scene); None: nothing of it runs."""
     kind = _kind(detector)
     if kind not in ('cont-det3d', 'cont-occ'):
         raise ValueError(f'{type(detector).__name__} has no walk session: use run_scene')
@@ -413,6 +501,7 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
         paint = _prediction_painter(render, detector, class_names, dscan)
     else:
         paint = _track_painter(render, detector, class_names, dscan, table)
+    paint_map = None if map is None else _map_painter(map, detector, class_names, dscan, map_cell, map_z, table)
     for t, frame in frames:
         res = walk.observe(*frame)
         res = res if kind == 'cont-occ' else _filtered(detector, res, filter)
@@ -421,6 +510,8 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
             res.track_hits, res.track_first_seen = table.lookup(res.track_ids)
         if paint is not None:
             paint(res, t)
+        if paint_map is not None:
+            paint_map(res, t)
         yield t, res
 
 
@@ -566,6 +657,9 @@ def main(argv=None):
     ap.add_argument('--topk', type=int, default=1, help='answers per prompt (grounding models)')
     ap.add_argument('--out', default=None, help='JSON file (default: standard output)')
     ap.add_argument('--render', default=None, metavar='DIR', help='write every frame under its prediction as DIR/frame_0000.png ... and DIR/legend.json')
+    ap.add_argument('--map', default=None, metavar='DIR', help='write the scene seen from above as DIR/map.png (--walk: DIR/map_0000.png ...), DIR/map.json and DIR/legend.json')
+    ap.add_argument('--map-cell', type=float, default=None, metavar='M', help='side of a map cell in metres (default: 0.02)')
+    ap.add_argument('--map-z', type=float, nargs=2, default=None, metavar=('ZMIN', 'ZMAX'), help='the map shows points with ZMIN <= z < ZMAX (default: -1 2)')
     ap.add_argument('--track', action='store_true', help='with --walk on a cont-det3d configuration: stable object identities over the walk (track_ids)')
     ap.add_argument('--track-iou', type=float, default=None, metavar='X', help='a detection continues a track above this IoU (default: 0.25)')
     ap.add_argument('--track-max-age', type=int, default=None, metavar='K', help='a track unmatched for more than K frames dies (default: never)')
@@ -583,6 +677,11 @@ def main(argv=None):
         ap.error(f"{cfg['model']['type']} grounds prompts: give --prompt TEXT (repeatable) or --prompts-file F")
     if prompts and not grounder:
         ap.error(f"{cfg['model']['type']} takes no prompt: --prompt / --prompts-file go with a grounding configuration")
+    if grounder and a.map is not None:
+        ap.error('--map goes with the detection and occupancy configurations (a grounding run draws its answers with --render)')
+    if a.map is None and (a.map_cell is not None or a.map_z is not None):
+        ap.error('--map-cell / --map-z shape the map that --map DIR writes: give --map DIR')
+    mp = dict(map=a.map, map_cell=0.02 if a.map_cell is None else a.map_cell, map_z=(-1.0, 2.0) if a.map_z is None else tuple(a.map_z))
     tracked = a.track or a.track_iou is not None or a.track_max_age is not None
     if tracked:                                                          # (refused before the model is built as well)
         cls = MODELS.get(cfg['model']['type'])
@@ -608,12 +707,12 @@ def main(argv=None):
     if a.walk and tracked:
         trk = dict(({} if a.track_iou is None else dict(iou_thr=a.track_iou)), **({} if a.track_max_age is None else dict(max_age=a.track_max_age)))
         results = [_record(r, names, t=t, track_ids=r.track_ids.cpu().tolist())
-                   for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, track=trk)]
+                   for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, track=trk, **mp)]
         return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=True, filter=flt, track=trk, results=results))
     if a.walk:
-        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names)]
+        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, **mp)]
     else:
-        results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names))]
+        results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, **mp))]
     return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt, results=results))
 
 

@@ -887,6 +887,39 @@ int es_render_occupancy(const unsigned char* src, int chw, int V, int H, int W, 
                         int X, int Y, int Z, const double* grid_host /*rmin[3], size[3]*/, const unsigned char* palette /*(C,3)*/, int C,
                         int alpha, unsigned char* dst, void* stream);
 
+/* ---- the scene seen from above (csrc/predict.hip) ---------------------------------------------------------------
+ * A map of Wm x Hm cells of `cell` metres whose lower-left corner is (x0, y0) of the aligned frame: cell (ix, iy) covers
+ * [x0 + ix*cell, x0 + (ix+1)*cell) x [y0 + iy*cell, y0 + (iy+1)*cell) and is image row Hm - 1 - iy, column ix (+y points up).
+ * grid_host = x0, y0, cell, z_min, z_max, max_depth: six f64 read on the HOST at the call.  The state is one u64 key per cell, (Hm, Wm),
+ * held as int64 (keys stay below 2^47, so signed and unsigned order agree); 0 = empty.  The exact operation order of all four kernels is
+ * written once at each kernel and restated by tests/scene_map_spec.py.
+ * es_map_splat: one thread per depth pixel of depth (V,H,W) f32 metres, f64 throughout.  frames u8 at (h, w), (V,3,h,w) with chw != 0 or
+ *   (V,h,w,3); rays (V,12) f64 = the 3x3 R^T K^-1 (row-major) and the camera centre, formed by the caller from the extrinsic and the
+ *   intrinsic AT THE DEPTH MAPS' RESOLUTION.  A pixel with 0 < d <= max_depth lands at p = c + d * (M (x, y, 1)) -- no half pixel, the cloud
+ *   of es_depth_to_points -- and, with z_min <= p_z < z_max and its cell inside the grid, raises that cell's key to
+ *   (zq + 1) << 24 | r << 16 | g << 8 | b, zq = floor((p_z - z_min) * 1024), (r, g, b) = the nearest frame pixel
+ *   ((2x+1)*w / (2W), (2y+1)*h / (2H)).  An integer max: the highest point wins, ties on zq go to the larger packed colour, and the result
+ *   depends on no thread order and on no order or grouping of the views.  keys is NOT cleared: the caller zeroes it to start a map.
+ * es_map_resolve: keys -> image (Hm,Wm,3) u8 and, with height != NULL, (Hm,Wm) f32 metres z_min + (zq + 0.5) / 1024 (NaN: empty); image may be
+ *   NULL when only the height map is wanted.  An empty
+ *   cell takes background (r << 16 | g << 8 | b); with shade != 0 a colour byte c becomes (c*s + 128) >> 8, s = 160 + 96*min(zq, span)/span,
+ *   span = max(1, ceil((z_max - z_min) * 1024) - 1): higher is brighter.
+ * es_map_project: one thread per box: rec (n, ES_RENDER_REC) as es_render_project writes it, for the orthographic view from above:
+ *   u = (X - x0) / cell, v = Hm - (Y - y0) / cell, the same quarter-pixel rounding and guard band |u|, |v| <= 4096; the skip bit is 0.  The
+ *   record feeds es_render_boxes(src = the map image, chw = 0, V = 1, ...) unchanged; a zero-size box draws a disc (the camera trail).
+ * es_map_occupancy: in place on image (Hm,Wm,3): the centre of every map pixel picks a column of occ (X,Y,Z) u8 over volume_host = rmin[3],
+ *   size[3]; the highest voxel with 1 <= label < C blends palette[label] with the image's weight alpha / 256; no such voxel: not written.
+ * Status: -4, nothing written and nothing launched, for a side (Wm, Hm, H, W, h, w) outside 1 .. 4096, cell <= 0, infinite or NaN, z_max <= z_min or a
+ *   z range above 4096 m, max_depth <= 0, background outside 0 .. 0xffffff, image and height both NULL, alpha outside 0 .. 256, C outside 1 .. 256, a volume dimension
+ *   < 1 or a voxel size <= 0, V > 65535, a negative count.  V = 0 or n = 0 is not an error. */
+int es_map_splat(const float* depth /*(V,H,W)*/, int V, int H, int W, const unsigned char* frames, int chw, int h, int w,
+                 const double* rays /*(V,12)*/, const double* grid_host, int Wm, int Hm, long long* keys /*(Hm,Wm)*/, void* stream);
+int es_map_resolve(const long long* keys, int Wm, int Hm, const double* grid_host, int background, int shade, unsigned char* image /*(Hm,Wm,3) or NULL*/,
+                   float* height /*(Hm,Wm) or NULL*/, void* stream);
+int es_map_project(const float* boxes /*(n,9)*/, int n, const double* grid_host, int Wm, int Hm, int* rec /*(n,ES_RENDER_REC)*/, void* stream);
+int es_map_occupancy(unsigned char* image /*(Hm,Wm,3)*/, int Wm, int Hm, const double* grid_host, const unsigned char* occ /*(X,Y,Z)*/, int X, int Y,
+                     int Z, const double* volume_host /*rmin[3], size[3]*/, const unsigned char* palette /*(C,3)*/, int C, int alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
