@@ -672,3 +672,260 @@ extern "C" int es_map_occupancy(unsigned char* image, int Wm, int Hm, const doub
   ES_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------ the scene in three dimensions
+// The recording's depth pixels fused into ONE de-duplicated coloured cloud: es_cloud_splat inserts every pixel's voxel key into an open
+// addressing table (tkeys / tvals / thits), es_cloud_mask marks the occupied slots with enough hits -- es_compact_mask and es_sort_u64
+// then list them in ascending key order, whatever the table layout --, es_cloud_points turns the sorted rows into voxel centres, colours
+// and hit counts, es_cloud_label gives every point the first 9-DoF box that holds it and every box its number of points, and
+// es_occ_face_mask / es_occ_face_quads list the exposed faces of a label volume as quads.  As above: int32 / int64 and plain f64 only;
+// the atomics are a CAS that can only turn -1 into a key, an integer max and integer adds, none of which depends on arrival order as
+// long as no pixel is dropped (a dropped pixel is COUNTED: counters[1]).  tests/scene_cloud_spec.py restates all six.
+struct CloudGrid { double cell, zmin, zmax, maxd; };
+
+// One thread per depth pixel (x, y) of view v, f64.  d, p_k and the colour pixel exactly as k_map_splat; kept iff z_min <= p_z < z_max;
+//   i_k = floor(p_k / cell), kept iff -2^17 <= i_k < 2^17 (compared in f64);  key = es_pack(0, i_x, i_y, i_z)
+//   dq = (int)floor(d * 256);  val = (u64)(2^21 - dq) << 24 | r << 16 | g << 8 | b      (max_depth <= 4096: dq <= 2^20)
+// Neighbouring pixels of an image row mostly fall into one voxel, so the lanes of a wave first combine their RUNS of equal keys: lane l
+// starts a run when l == 0 or the key of lane l - 1 differs (a dropped pixel carries key -1: its runs are never inserted); the start
+// lane takes the run's max val by a segmented shuffle reduction and its length from the boundary ballot, and alone probes the table:
+//   s = es_hash(key, cap - 1); up to `probes` = min(64, cap) slots, linearly: CAS(tkeys[s], -1, key) returns -1 or key ->
+//   tvals[s] = max(itself, val), thits[s] += length, done;  after the last probe the run is dropped and nothing is written for it.
+// counters[0] / [1] += the wave's inserted / dropped pixels, one add per wave each (ballot + popcount).  Max and add are associative:
+// the table bits equal those of one CAS / max / add per pixel (that variant was measured and is gone).  A slot is read
+// before the CAS and the max (relaxed, agent scope): a key never changes once set and a stale val can only be too small.
+__global__ __launch_bounds__(256) void k_cloud_splat(const float* __restrict__ depth, int H, int W, const unsigned char* __restrict__ frames,
+                                                     int chw, int h, int w, const double* __restrict__ rays, CloudGrid G,
+                                                     unsigned long long* tkeys, unsigned long long* tvals, unsigned int* thits,
+                                                     uint32_t mask, int probes, unsigned int* counters) {
+  const int v = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  long long key = -1;
+  unsigned long long val = 0;
+  if (p < H * W) {
+    const int y = p / W, x = p - y * W;
+    const double d = (double)depth[(size_t)v * H * W + p];
+    if (d > 0.0 && d <= G.maxd) {
+      const double* M = rays + (size_t)v * 12;
+      const double fx = (double)x, fy = (double)y;
+      double q[3], c[3];
+      for (int k = 0; k < 3; ++k) q[k] = M[9 + k] + d * ((M[k * 3] * fx + M[k * 3 + 1] * fy) + M[k * 3 + 2]);
+      for (int k = 0; k < 3; ++k) c[k] = floor(q[k] / G.cell);
+      const double lo = -(double)ES_OFF, hi = (double)ES_OFF;
+      if (q[2] >= G.zmin && q[2] < G.zmax && c[0] >= lo && c[0] < hi && c[1] >= lo && c[1] < hi && c[2] >= lo && c[2] < hi) {
+        int r, g, b;
+        rnd_load(frames, chw, v, h, w, ((2 * y + 1) * h) / (2 * H), ((2 * x + 1) * w) / (2 * W), r, g, b);
+        const int dq = (int)floor(d * 256.0);
+        key = es_pack(0, (int)c[0], (int)c[1], (int)c[2]);
+        val = ((unsigned long long)((1 << 21) - dq) << 24) | ((unsigned long long)r << 16) | ((unsigned long long)g << 8) | (unsigned long long)b;
+      }
+    }
+  }
+  // every lane of the wave is here (no early return above): the run boundaries, then the run's max in its start lane
+  const long long prev = __shfl_up(key, 1);
+  const unsigned long long bounds = __ballot(lane == 0 || prev != key);
+  const int start = 63 - __builtin_clzll(bounds & (~0ull >> (63 - lane)));
+  const unsigned long long above = (bounds >> start) >> 1;
+  const int end = above ? start + 1 + __builtin_ctzll(above) : 64;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long other = __shfl_down(val, o);
+    if (lane + o < end && other > val) val = other;
+  }
+  int placed = 0;
+  if (key >= 0 && lane == start) {
+    uint32_t s = es_hash(key, mask);
+    for (int it = 0; it < probes; ++it) {
+      unsigned long long o = __hip_atomic_load(tkeys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (o == ~0ull) o = atomicCAS(tkeys + s, ~0ull, (unsigned long long)key);
+      if (o == ~0ull || o == (unsigned long long)key) {
+        if (__hip_atomic_load(tvals + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < val) atomicMax(tvals + s, val);
+        atomicAdd(thits + s, (unsigned int)(end - start));
+        placed = 1;
+        break;
+      }
+      s = (s + 1) & mask;
+    }
+  }
+  placed = __shfl(placed, start);
+  const unsigned long long in = __ballot(key >= 0 && placed), out = __ballot(key >= 0 && !placed);
+  if (lane == 0) {
+    if (in) atomicAdd(counters, (unsigned int)__popcll(in));
+    if (out) atomicAdd(counters + 1, (unsigned int)__popcll(out));
+  }
+}
+
+// mask[s] = 1 iff slot s holds a key and thits[s] >= min_hits, else 0
+__global__ void k_cloud_mask(const long long* __restrict__ tkeys, const unsigned int* __restrict__ thits, int cap, unsigned int min_hits,
+                             int* __restrict__ mask) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= cap) return;
+  mask[s] = (tkeys[s] != ES_EMPTY_KEY && thits[s] >= min_hits) ? 1 : 0;
+}
+
+// Row j of the sorted cloud, slot s = src[j]: xyz = the voxel's centre (float)(((double)i_k + 0.5) * cell), rgb = the low three bytes of
+// tvals[s], hits = min(thits[s], 2^31 - 1)
+__global__ void k_cloud_points(const long long* __restrict__ keys, const int* __restrict__ src, int n,
+                               const unsigned long long* __restrict__ tvals, const unsigned int* __restrict__ thits, double cell,
+                               float* __restrict__ xyz, unsigned char* __restrict__ rgb, int* __restrict__ hits) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int b, i[3];
+  es_unpack(keys[j], b, i[0], i[1], i[2]);
+  const int s = src[j];
+  const unsigned long long val = tvals[s];
+  for (int k = 0; k < 3; ++k) xyz[(size_t)j * 3 + k] = (float)(((double)i[k] + 0.5) * cell);
+  rgb[(size_t)j * 3] = (unsigned char)(val >> 16);
+  rgb[(size_t)j * 3 + 1] = (unsigned char)(val >> 8);
+  rgb[(size_t)j * 3 + 2] = (unsigned char)val;
+  const unsigned int t = thits[s];
+  hits[j] = t > 0x7fffffffu ? 0x7fffffff : (int)t;
+}
+
+// One thread per point, the boxes staged through LDS RND_CHUNK at a time (lane i of wave 0 stages box i of the chunk, f64: centre,
+// half + grow, and R with half, R, cos / sin as k_render_project), so m is not limited by LDS.  dx = (double)p - c;
+//   l_k = (R[0][k]*dx_0 + R[1][k]*dx_1) + R[2][k]*dx_2;  inside iff -(half_k + grow) <= l_k <= half_k + grow for k = 0, 1, 2
+// label[i] = the smallest such j, else -1 (a point stops testing at its first hit); support[j] += 1 through a per-workgroup LDS count
+// that is flushed once per chunk: integer adds only.
+__global__ __launch_bounds__(256) void k_cloud_label(const float* __restrict__ xyz, int n, const float* __restrict__ boxes, int m, double grow,
+                                                     int* __restrict__ label, int* __restrict__ support) {
+  __shared__ double s_box[RND_CHUNK][15];
+  __shared__ int s_cnt[RND_CHUNK];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double pt[3] = {0.0, 0.0, 0.0};
+  if (i < n)
+    for (int k = 0; k < 3; ++k) pt[k] = (double)xyz[(size_t)i * 3 + k];
+  int found = -1;
+  for (int j0 = 0; j0 < m; j0 += RND_CHUNK) {
+    const int cnt = min(RND_CHUNK, m - j0);
+    if ((int)threadIdx.x < cnt) {
+      const float* b = boxes + (size_t)(j0 + threadIdx.x) * 9;
+      double* o = s_box[threadIdx.x];
+      const double ca = cos((double)b[6]), sa = sin((double)b[6]), cb = cos((double)b[7]), sb = sin((double)b[7]);
+      const double cc = cos((double)b[8]), sc = sin((double)b[8]);
+      for (int k = 0; k < 3; ++k) { o[k] = (double)b[k]; o[3 + k] = (double)b[3 + k] * 0.5 + grow; }
+      o[6] = ca * cc - sa * sb * sc; o[7] = -(sa * cb); o[8] = ca * sc + sa * sb * cc;
+      o[9] = sa * cc + ca * sb * sc; o[10] = ca * cb; o[11] = sa * sc - ca * sb * cc;
+      o[12] = -(cb * sc); o[13] = sb; o[14] = cb * cc;
+      s_cnt[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    if (i < n && found < 0) {
+      for (int j = 0; j < cnt; ++j) {
+        const double* o = s_box[j];
+        const double dx[3] = {pt[0] - o[0], pt[1] - o[1], pt[2] - o[2]};
+        bool inside = true;
+        for (int k = 0; k < 3; ++k) {
+          const double l = (o[6 + k] * dx[0] + o[9 + k] * dx[1]) + o[12 + k] * dx[2];
+          inside = inside && (l <= o[3 + k]) && (l >= -o[3 + k]);
+        }
+        if (inside) { found = j0 + j; atomicAdd(&s_cnt[j], 1); break; }
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cnt && s_cnt[threadIdx.x]) atomicAdd(support + j0 + threadIdx.x, s_cnt[threadIdx.x]);
+    __syncthreads();
+  }
+  if (i < n) label[i] = found;
+}
+
+// Element e = 6 * ((i*Y + j)*Z + k) + f, f = -x, +x, -y, +y, -z, +z: set iff 1 <= occ[i][j][k] < C and the neighbour across face f lies
+// outside the volume or holds no such label
+__global__ void k_occ_face_mask(const unsigned char* __restrict__ occ, int X, int Y, int Z, int C, int* __restrict__ mask) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 6 * X * Y * Z) return;
+  const int f = e % 6, cell = e / 6, k = cell % Z, j = (cell / Z) % Y, i = cell / (Y * Z);
+  const int l = occ[cell];
+  int set = 0;
+  if (l >= 1 && l < C) {
+    const int a = f >> 1, step = (f & 1) ? 1 : -1;
+    const int ni = i + (a == 0 ? step : 0), nj = j + (a == 1 ? step : 0), nk = k + (a == 2 ? step : 0);
+    set = 1;
+    if (ni >= 0 && ni < X && nj >= 0 && nj < Y && nk >= 0 && nk < Z) {
+      const int o = occ[((size_t)ni * Y + nj) * Z + nk];
+      set = !(o >= 1 && o < C);
+    }
+  }
+  mask[e] = set;
+}
+
+// the corners of face f as bits (x | y << 1 | z << 2) of the voxel's unit cube, counter-clockwise seen from outside, three bits per corner
+#define OCC_QUAD(a, b, c, d) ((a) | (b) << 3 | (c) << 6 | (d) << 9)
+__host__ __device__ constexpr int occ_face_corners(int f) {
+  return f == 0 ? OCC_QUAD(0, 4, 6, 2) : f == 1 ? OCC_QUAD(1, 3, 7, 5) : f == 2 ? OCC_QUAD(0, 1, 5, 4) : f == 3 ? OCC_QUAD(2, 6, 7, 3)
+       : f == 4 ? OCC_QUAD(0, 2, 3, 1) : OCC_QUAD(4, 5, 7, 6);
+}
+
+// Face row r = element e = src[r]: verts[4r + q][a] = (float)(rmin_a + (double)(index_a + bit_a) * size_a), face_label[r] = the voxel's label
+__global__ void k_occ_face_quads(const unsigned char* __restrict__ occ, RndGrid O, const int* __restrict__ src, int n, float* __restrict__ verts,
+                                 unsigned char* __restrict__ face_label) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const int e = src[r], f = e % 6, cell = e / 6;
+  const int idx[3] = {cell / (O.n[1] * O.n[2]), (cell / O.n[2]) % O.n[1], cell % O.n[2]};
+  const int corners = occ_face_corners(f);
+  for (int q = 0; q < 4; ++q) {
+    const int bits = (corners >> (3 * q)) & 7;
+    for (int a = 0; a < 3; ++a) verts[((size_t)r * 4 + q) * 3 + a] = (float)(O.rmin[a] + (double)(idx[a] + ((bits >> a) & 1)) * O.size[a]);
+  }
+  face_label[r] = occ[cell];
+}
+
+extern "C" int es_cloud_splat(const float* depth, int V, int H, int W, const unsigned char* frames, int chw, int h, int w, const double* rays,
+                              const double* grid_host, int64_t* tkeys, uint64_t* tvals, unsigned int* thits, int cap, unsigned int* counters,
+                              void* stream) {
+  if (V < 0) return -5;
+  CloudGrid G = {grid_host[0], grid_host[1], grid_host[2], grid_host[3]};
+  if (V > 65535 || !rnd_frame_ok(H, W) || !rnd_frame_ok(h, w) || cap < 2 || cap > (1 << 30) || (cap & (cap - 1)) ||
+      !(G.cell > 0.0 && G.cell < __builtin_inf()) || !(G.maxd > 0.0 && G.maxd <= 4096.0) || !(G.zmax > G.zmin))
+    return -4;
+  if (V == 0) return 0;
+  hipLaunchKernelGGL(k_cloud_splat, dim3(es_cdiv(H * W, 256), V), dim3(256), 0, (hipStream_t)stream, depth, H, W, frames, chw, h, w, rays, G,
+                     (unsigned long long*)tkeys, (unsigned long long*)tvals, thits, (uint32_t)cap - 1, cap < ES_CLOUD_PROBES ? cap : ES_CLOUD_PROBES,
+                     counters);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_cloud_mask(const int64_t* tkeys, const unsigned int* thits, int cap, int min_hits, int* mask, void* stream) {
+  if (cap < 2 || cap > (1 << 30) || (cap & (cap - 1)) || min_hits < 0) return -4;
+  hipLaunchKernelGGL(k_cloud_mask, dim3(es_cdiv(cap, 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)tkeys, thits, cap,
+                     (unsigned int)min_hits, mask);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_cloud_points(const int64_t* sorted_keys, const int* src, int n, const uint64_t* tvals, const unsigned int* thits, double cell,
+                               float* xyz, unsigned char* rgb, int* hits, void* stream) {
+  if (n < 0) return -5;
+  if (n > (1 << 30) || !(cell > 0.0 && cell < __builtin_inf())) return -4;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_cloud_points, dim3(es_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)sorted_keys, src, n,
+                     (const unsigned long long*)tvals, thits, cell, xyz, rgb, hits);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_cloud_label(const float* xyz, int n, const float* boxes, int m, double grow, int* label, int* support, void* stream) {
+  if (n < 0 || m < 0) return -5;
+  if (n > (1 << 30) || m > 65535 || !(grow >= 0.0 && grow < __builtin_inf())) return -4;
+  if (m > 0) ES_TRY(hipMemsetAsync(support, 0, (size_t)m * 4, (hipStream_t)stream));
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_cloud_label, dim3(es_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, xyz, n, boxes, m, grow, label, support);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+static inline bool occ_volume_ok(int X, int Y, int Z) { return X >= 1 && Y >= 1 && Z >= 1 && 6ll * X * Y * Z <= (1ll << 30); }
+extern "C" int es_occ_face_mask(const unsigned char* occ, int X, int Y, int Z, int C, int* mask, void* stream) {
+  if (C < 1 || C > 256 || !occ_volume_ok(X, Y, Z)) return -4;
+  hipLaunchKernelGGL(k_occ_face_mask, dim3(es_cdiv(6ll * X * Y * Z, 256)), dim3(256), 0, (hipStream_t)stream, occ, X, Y, Z, C, mask);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int es_occ_face_quads(const unsigned char* occ, int X, int Y, int Z, const double* vol_host, const int* src, int n, float* verts,
+                                 unsigned char* face_label, void* stream) {
+  if (n < 0) return -5;
+  if (!occ_volume_ok(X, Y, Z) || n > 6ll * X * Y * Z) return -4;
+  if (n == 0) return 0;
+  RndGrid O;
+  for (int i = 0; i < 3; ++i) { O.rmin[i] = vol_host[i]; O.size[i] = vol_host[3 + i]; }
+  O.n[0] = X; O.n[1] = Y; O.n[2] = Z;
+  hipLaunchKernelGGL(k_occ_face_quads, dim3(es_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, occ, O, src, n, verts, face_label);
+  ES_CHECK_LAUNCH();
+  return 0;
+}

@@ -3,6 +3,7 @@ the model consumed: the reference's demo (demo/demo.py) without the 3-D viewer.
 
     python -m embodiedscan_amd.inference CONFIG [CHECKPOINT] --root-dir D --scene S [--walk] [--out F.json] [--render DIR]
                                          [--map DIR [--map-cell M] [--map-z ZMIN ZMAX]] [--track [--track-iou X] [--track-max-age K]]
+                                         [--cloud DIR [--cloud-cell M] [--cloud-min-hits N] [--cloud-every K]]
 
 reads D/S/{poses.txt, intrinsic.txt, axis_align_matrix.txt, rgb/<timestamp>.jpg, depth/<timestamp>.png}, runs the model of CONFIG in
 `predict` mode (or frame by frame through a walk session with --walk) and writes the filtered boxes, scores, labels and class names
@@ -24,6 +25,13 @@ boxes' footprints (or the final volume's top surface) and the trail of the camer
 max_depth: a pixel maps back to metres) and DIR/legend.json; walk_scene writes map_0000.png ...: map t holds frames 0 .. t, the prediction of
 prefix t and the trail so far.  The grid is fixed before the first frame: the rectangle of all camera centres grown by 8 m (detectors) or the
 xy rectangle of point_cloud_range (occupancy).  With map=None nothing of it runs.
+
+cloud=DIR (run_scene, walk_scene, --cloud [--cloud-cell M] [--cloud-min-hits N] [--cloud-every K]): the scene in three dimensions as
+binary PLY files that MeshLab, CloudCompare, Blender or open3d open (embodiedscan_amd.scene_cloud): DIR/scene.ply, the
+recording's depth pixels fused on the device into one coloured point per voxel of M metres, every point labelled with the class and the
+row (--track: the track id) of the detection that contains it; DIR/boxes.ply, the boxes' wireframes, or DIR/occupancy.ply, the exposed
+voxel faces of the volume; DIR/cloud.json.  The records of a labelled list gain `support`, the number of points inside each box.  With
+cloud=None nothing of it runs.
 
 --track (with --walk, the cont-det3d model; walk_scene(track=dict(...))): a tracks.TrackTable is updated with every frame's filtered list,
 the records gain track_ids -- the same object keeps its id from frame to frame -- and --render colours by track (legend.json: track_<id> ->
@@ -48,6 +56,7 @@ import torch
 from . import hip
 from . import pipeline as PL
 from . import render as RD
+from . import scene_cloud as SC
 from . import scene_map as SM
 from .structures import EulerDepthInstance3DBoxes, InstanceData
 
@@ -349,13 +358,17 @@ def _filtered(detector, inst, filter):
     return filter_instances(inst, **dict(dict(n_classes=detector.bbox_head.num_classes), **filter))
 
 
-def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None, class_names=None, map=None, map_cell=0.02, map_z=(-1.0, 2.0)):
+def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None, class_names=None, map=None, map_cell=0.02, map_z=(-1.0, 2.0),
+              cloud=None, cloud_cell=0.02, cloud_min_hits=1):
     """one `predict` over the folder.  Detectors: the filtered InstanceData per sample (the cont-det3d detector: one per prefix);
     occupancy models: pred_occupancy per sample / prefix.  filter: keyword arguments of filter_instances; None: the raw prediction.
     render: a directory that receives every view of the scan under the final list / volume (the last prefix's for the continuous kinds)
     as frame_0000.png ... and legend.json; None: nothing is drawn.
     map: a directory that receives map.png, map.json and legend.json -- the whole recording seen from above under that same final
-    prediction, in cells of map_cell metres, showing z in [map_z[0], map_z[1]); None: nothing of it runs."""
+    prediction, in cells of map_cell metres, showing z in [map_z[0], map_z[1]); None: nothing of it runs.
+    cloud: a directory that receives scene.ply -- every view's depth pixels fused into one voxel of cloud_cell metres each (those that at
+    least cloud_min_hits pixels fell into), labelled by that same final prediction --, boxes.ply or occupancy.ply and cloud.json
+    (_cloud_writer); the final InstanceData gains cloud_support; None: nothing of it runs."""
     kind = _kind(detector)
     dscan = load_scene(detector, scene_dir, pipeline, seed)
     data = detector.data_preprocessor(make_scene_batch(detector, dscan), False)
@@ -368,6 +381,10 @@ def run_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), render=None,
         _prediction_painter(render, detector, class_names, dscan)(res[-1])
     if map is not None:
         _map_painter(map, detector, class_names, dscan, map_cell, map_z)(res[-1])
+    if cloud is not None:
+        join, write = _cloud_writer(cloud, detector, class_names, dscan, cloud_cell, cloud_min_hits)
+        join(None)
+        write(res[-1])
     return res
 
 
@@ -474,8 +491,63 @@ def _map_painter(dir, detector, class_names, dscan, cell, z, table=None, max_dep
     return paint
 
 
+def _cloud_writer(dir, detector, class_names, dscan, cell, min_hits, table=None, capacity=1 << 22, max_depth=8.0):
+    """the scene in three dimensions as files (scene_cloud) -> (join(t), write(res, t=None)).  join(t) fuses frame t of the scan
+    into the cloud (None: every frame).  write(res) writes, under the prediction `res`, dir/scene.ply -- vertex properties x y z red green
+    blue hits label instance: detectors: label = the class of the first box of the list that holds the point, instance = that box's row in
+    the list (table: its track id), both -1 outside every box; occupancy kinds: both -1 --, dir/boxes.ply (the boxes' wireframes in their
+    class colour; table: their track's) or dir/occupancy.ply (the volume's exposed faces in the class palette) and dir/cloud.json (cell,
+    capacity, counters, rows, class names and colours, the boxes' support); with t the files are scene_<t>.ply ...; an InstanceData gains
+    cloud_support (m,) int32 on the device.  scene_cloud.CloudFull when the table dropped a pixel."""
+    os.makedirs(dir, exist_ok=True)
+    dev = detector.device
+    E, K = depth_matrices(dscan)
+    cl = SC.SceneCloud(dev, cell, capacity, max_depth=max_depth)
+    names, pal = _class_legend(detector, class_names)
+    track_pal = RD.class_palette(TRACK_PALETTE)[1:]
+
+    def join(t):
+        v = slice(None) if t is None else slice(t, t + 1)
+        cl.add(dscan['depth'][v], dscan['img'][v], E[v], K[v], layout='chw')
+
+    def write(res, t=None):
+        sfx = '' if t is None else f'_{t:04d}'
+        xyz, rgb, hits = cl.points(min_hits)
+        n = int(xyz.shape[0])
+        doc = dict(cell=cl.cell, capacity=cl.capacity, min_hits=int(min_hits), counters=list(cl.pixel_counts()), rows=n, class_names=list(names),
+                   class_colors=[[int(c) for c in row] for row in pal])
+        if isinstance(res, InstanceData):
+            row, support = SC.label(xyz, res.bboxes_3d)
+            res.cloud_support = support
+            hit = row.long().clamp(min=0)
+            m = int(support.shape[0])
+            lab_of = res.labels_3d.to(torch.int32) if m else torch.zeros(1, dtype=torch.int32, device=dev)
+            ins_of = res.track_ids.to(torch.int32) if (table is not None and m) else None
+            minus = torch.full_like(row, -1)
+            label = torch.where(row >= 0, lab_of[hit if m else torch.zeros_like(hit)], minus)
+            instance = row if ins_of is None else torch.where(row >= 0, ins_of[hit], minus)
+            labels = res.labels_3d.long().cpu().numpy()
+            if table is not None:
+                colors = track_pal[res.track_ids.cpu().numpy() % 256]
+                doc['track_ids'] = res.track_ids.cpu().tolist()
+            else:
+                colors = pal[np.clip(labels, 0, len(pal) - 1)]
+            bv, be, bc = SC.box_edges(getattr(res.bboxes_3d, 'tensor', res.bboxes_3d), np.ascontiguousarray(colors, np.uint8).reshape(-1, 3))
+            SC.write_ply(os.path.join(dir, f'boxes{sfx}.ply'), SC.vertex_columns(bv.astype(np.float32)), edge=(be, bc))
+            doc.update(labels=labels.tolist(), support=support.cpu().tolist())
+        else:
+            label = instance = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            verts, quads, face_label, colors = SC.occupancy_mesh(res, detector.point_cloud_range, pal)
+            SC.write_ply(os.path.join(dir, f'occupancy{sfx}.ply'), SC.vertex_columns(verts, colors), face=quads)
+            doc.update(faces=int(quads.shape[0]))
+        SC.write_ply(os.path.join(dir, f'scene{sfx}.ply'), SC.vertex_columns(xyz, rgb, hits=hits, label=label, instance=instance))
+        with open(os.path.join(dir, 'cloud.json'), 'w') as f:
+            json.dump(doc, f)
+    return join, write
+
+
 def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=None, render=None, class_names=None, track=None, map=None,
-               map_cell=0.02, map_z=(-1.0, 2.0)):
+               map_cell=0.02, map_z=(-1.0, 2.0), cloud=None, cloud_cell=0.02, cloud_min_hits=1, cloud_every=0):
     """generator over the frames of the folder for the two continuous models (the reference's render_continuous_scene): opens a walk
     session, feeds it frame by frame and yields (t, filtered InstanceData) or (t, pred_occupancy).  render: a directory that receives
     frame t under the prediction of prefix t as frame_<t>.png, and legend.json; None: nothing is drawn.
@@ -483,14 +555,18 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
     every frame, and the yielded InstanceData gain track_ids (int64; -1: the table was full), track_hits and track_first_seen, all on the
     device; with render the boxes take their track's colour (_track_painter).  None: no table, nothing of it runs.
     map: a directory that receives map_<t>.png -- frames 0 .. t seen from above under the prediction of prefix t and the trail so far, on
-    a grid fixed before the first frame from all of the folder's poses --, map.json and legend.json (run_scene); None: nothing of it runs."""
+    a grid fixed before the first frame from all of the folder's poses --, map.json and legend.json (run_scene); None: nothing of it runs.
+    cloud: a directory for the scene in three dimensions (_cloud_writer): frame t joins the cloud after its observe; with cloud_every > 0 the
+    frames t % cloud_every == 0 write scene_<t>.ply (+ boxes_<t>.ply / occupancy_<t>.ply) under the prediction of prefix t, and the last
+    frame writes the un-numbered files under the last prefix's prediction -- both before the frame is yielded, so that a labelled
+    InstanceData carries cloud_support; None: nothing of it runs."""
     kind = _kind(detector)
     if kind not in ('cont-det3d', 'cont-occ'):
         raise ValueError(f'{type(detector).__name__} has no walk session: use run_scene')
     if track is not None and kind != 'cont-det3d':
         raise ValueError(f'{type(detector).__name__} yields no object list: track= goes with the cont-det3d detector')
     dscan = load_scene(detector, scene_dir, pipeline, seed)
-    walk, _, frames = _scene_walk(detector, dscan, make_scene_batch(detector, dscan), max_frames, capped=kind == 'cont-det3d')
+    walk, n_frames, frames = _scene_walk(detector, dscan, make_scene_batch(detector, dscan), max_frames, capped=kind == 'cont-det3d')
     table = None
     if track is not None:
         from .tracks import TrackTable
@@ -502,6 +578,7 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
     else:
         paint = _track_painter(render, detector, class_names, dscan, table)
     paint_map = None if map is None else _map_painter(map, detector, class_names, dscan, map_cell, map_z, table)
+    join, write_cloud = (None, None) if cloud is None else _cloud_writer(cloud, detector, class_names, dscan, cloud_cell, cloud_min_hits, table)
     for t, frame in frames:
         res = walk.observe(*frame)
         res = res if kind == 'cont-occ' else _filtered(detector, res, filter)
@@ -512,6 +589,12 @@ def walk_scene(detector, scene_dir, pipeline, seed=0, filter=dict(), max_frames=
             paint(res, t)
         if paint_map is not None:
             paint_map(res, t)
+        if join is not None:
+            join(t)
+            if int(cloud_every) > 0 and t % int(cloud_every) == 0:
+                write_cloud(res, t)
+            if t == n_frames - 1:
+                write_cloud(res)
         yield t, res
 
 
@@ -618,6 +701,8 @@ def _class_names(cfg, n):
 def _record(res, names, **extra):
     if isinstance(res, InstanceData):
         labels = res.labels_3d.cpu().tolist()
+        if 'cloud_support' in res:                                       # (a cloud is kept and this list labelled it)
+            extra = dict(extra, support=res.cloud_support.cpu().tolist())
         return dict(extra, boxes=res.bboxes_3d.tensor.cpu().tolist(), scores=res.scores_3d.cpu().tolist(), labels=labels,
                     class_names=[names[l] for l in labels])
     hist = torch.bincount(res.reshape(-1)).cpu().tolist()
@@ -660,6 +745,10 @@ def main(argv=None):
     ap.add_argument('--map', default=None, metavar='DIR', help='write the scene seen from above as DIR/map.png (--walk: DIR/map_0000.png ...), DIR/map.json and DIR/legend.json')
     ap.add_argument('--map-cell', type=float, default=None, metavar='M', help='side of a map cell in metres (default: 0.02)')
     ap.add_argument('--map-z', type=float, nargs=2, default=None, metavar=('ZMIN', 'ZMAX'), help='the map shows points with ZMIN <= z < ZMAX (default: -1 2)')
+    ap.add_argument('--cloud', default=None, metavar='DIR', help='write the scene in three dimensions as DIR/scene.ply (the labelled colour cloud), DIR/boxes.ply or DIR/occupancy.ply and DIR/cloud.json')
+    ap.add_argument('--cloud-cell', type=float, default=None, metavar='M', help='side of a cloud voxel in metres (default: 0.02)')
+    ap.add_argument('--cloud-min-hits', type=int, default=None, metavar='N', help='keep the voxels that at least N depth pixels fell into (default: 1)')
+    ap.add_argument('--cloud-every', type=int, default=None, metavar='K', help='with --walk: also write DIR/scene_<t>.ply ... for every K-th frame (default: only the final files)')
     ap.add_argument('--track', action='store_true', help='with --walk on a cont-det3d configuration: stable object identities over the walk (track_ids)')
     ap.add_argument('--track-iou', type=float, default=None, metavar='X', help='a detection continues a track above this IoU (default: 0.25)')
     ap.add_argument('--track-max-age', type=int, default=None, metavar='K', help='a track unmatched for more than K frames dies (default: never)')
@@ -681,7 +770,15 @@ def main(argv=None):
         ap.error('--map goes with the detection and occupancy configurations (a grounding run draws its answers with --render)')
     if a.map is None and (a.map_cell is not None or a.map_z is not None):
         ap.error('--map-cell / --map-z shape the map that --map DIR writes: give --map DIR')
-    mp = dict(map=a.map, map_cell=0.02 if a.map_cell is None else a.map_cell, map_z=(-1.0, 2.0) if a.map_z is None else tuple(a.map_z))
+    if grounder and a.cloud is not None:
+        ap.error('--cloud goes with the detection and occupancy configurations')
+    if a.cloud is None and (a.cloud_cell is not None or a.cloud_min_hits is not None or a.cloud_every is not None):
+        ap.error('--cloud-cell / --cloud-min-hits / --cloud-every shape what --cloud DIR writes: give --cloud DIR')
+    if a.cloud_every is not None and not a.walk:
+        ap.error('--cloud-every numbers the clouds of a walk: it goes with --walk')
+    mp = dict(map=a.map, map_cell=0.02 if a.map_cell is None else a.map_cell, map_z=(-1.0, 2.0) if a.map_z is None else tuple(a.map_z),
+              cloud=a.cloud, cloud_cell=0.02 if a.cloud_cell is None else a.cloud_cell, cloud_min_hits=1 if a.cloud_min_hits is None else a.cloud_min_hits)
+    wk = dict(mp, cloud_every=a.cloud_every or 0)
     tracked = a.track or a.track_iou is not None or a.track_max_age is not None
     if tracked:                                                          # (refused before the model is built as well)
         cls = MODELS.get(cfg['model']['type'])
@@ -707,10 +804,10 @@ def main(argv=None):
     if a.walk and tracked:
         trk = dict(({} if a.track_iou is None else dict(iou_thr=a.track_iou)), **({} if a.track_max_age is None else dict(max_age=a.track_max_age)))
         results = [_record(r, names, t=t, track_ids=r.track_ids.cpu().tolist())
-                   for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, track=trk, **mp)]
+                   for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, track=trk, **wk)]
         return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=True, filter=flt, track=trk, results=results))
     if a.walk:
-        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, **mp)]
+        results = [_record(r, names, t=t) for t, r in walk_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, **wk)]
     else:
         results = [_record(r, names, t=t) for t, r in enumerate(run_scene(det, scene_dir, pipe, a.seed, flt, render=a.render, class_names=names, **mp))]
     return _emit(a, dict(scene=f'demo/{a.scene}', config=str(a.config), model=type(det).__name__, walk=bool(a.walk), filter=flt, results=results))

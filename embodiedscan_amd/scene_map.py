@@ -94,6 +94,39 @@ def _image(fn, grid, image, dev):
     return image
 
 
+def check_views(fn, device, depth, frames, extrinsic, intrinsic, layout=None, what='map'):
+    """the argument checks of SceneMap.add (scene_cloud.SceneCloud.add takes the same views) -> (V, H, W, chw, h, w, E, K)"""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3 or not depth.is_contiguous():
+        raise ValueError(f'{fn}: depth is a contiguous float32 (V, H, W) tensor, got {getattr(depth, "dtype", type(depth))} '
+                         f'{tuple(getattr(depth, "shape", ()))}')
+    if depth.device != device:
+        raise ValueError(f'{fn}: depth on {depth.device}, the {what} on {device}')
+    V, H, W = (int(s) for s in depth.shape)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous():
+        raise ValueError(f'{fn}: frames are a contiguous 4-d uint8 tensor, got {getattr(frames, "dtype", type(frames))} '
+                         f'{tuple(getattr(frames, "shape", ()))}')
+    if frames.device != device:
+        raise ValueError(f'{fn}: frames on {frames.device}, the {what} on {device}')
+    first, last = frames.shape[1] == 3, frames.shape[3] == 3
+    if layout is None:
+        if first == last:
+            raise ValueError(f'{fn}: frames of shape {tuple(frames.shape)} are neither clearly (V, 3, h, w) nor (V, h, w, 3): pass layout=')
+        layout = 'chw' if first else 'hwc'
+    if layout not in ('chw', 'hwc') or not (first if layout == 'chw' else last):
+        raise ValueError(f'{fn}: layout {layout!r} does not fit frames of shape {tuple(frames.shape)}')
+    chw = layout == 'chw'
+    h, w = (int(frames.shape[2]), int(frames.shape[3])) if chw else (int(frames.shape[1]), int(frames.shape[2]))
+    if int(frames.shape[0]) != V:
+        raise ValueError(f'{fn}: {int(frames.shape[0])} frames for {V} depth maps')
+    if V > 65535:
+        raise ValueError(f'{fn}: {V} views, one launch takes 65535')
+    for name, a, b in (('depth maps', H, W), ('frames', h, w)):
+        if not (1 <= a <= RD.MAX_SIDE and 1 <= b <= RD.MAX_SIDE):
+            raise ValueError(f'{fn}: {name} of {a} x {b} pixels, the kernel takes 1 .. {RD.MAX_SIDE} per side')
+    E, K = RD._matrices(fn, extrinsic, V, 'extrinsic'), RD._matrices(fn, intrinsic, V, 'intrinsic')
+    return V, H, W, chw, h, w, E, K
+
+
 class SceneMap:
     """the z-buffer of one map: (height, width) int64 keys on `device`, 0 = empty.  Depth pixels beyond max_depth metres are ignored."""
 
@@ -125,35 +158,7 @@ class SceneMap:
         """depth (V, H, W) f32 metres, frames u8 (V, 3, h, w) or (V, h, w, 3) of any size, both on the map's device; extrinsic / intrinsic
         (V, 4, 4) at the DEPTH maps' resolution.  Any number of views, any number of times, in any order: the map is the same.
         ValueError before any launch: a wrong dtype, shape, device or count, a side outside 1 .. 4096, more than 65535 views."""
-        fn = 'SceneMap.add'
-        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3 or not depth.is_contiguous():
-            raise ValueError(f'{fn}: depth is a contiguous float32 (V, H, W) tensor, got {getattr(depth, "dtype", type(depth))} '
-                             f'{tuple(getattr(depth, "shape", ()))}')
-        if depth.device != self.device:
-            raise ValueError(f'{fn}: depth on {depth.device}, the map on {self.device}')
-        V, H, W = (int(s) for s in depth.shape)
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous():
-            raise ValueError(f'{fn}: frames are a contiguous 4-d uint8 tensor, got {getattr(frames, "dtype", type(frames))} '
-                             f'{tuple(getattr(frames, "shape", ()))}')
-        if frames.device != self.device:
-            raise ValueError(f'{fn}: frames on {frames.device}, the map on {self.device}')
-        first, last = frames.shape[1] == 3, frames.shape[3] == 3
-        if layout is None:
-            if first == last:
-                raise ValueError(f'{fn}: frames of shape {tuple(frames.shape)} are neither clearly (V, 3, h, w) nor (V, h, w, 3): pass layout=')
-            layout = 'chw' if first else 'hwc'
-        if layout not in ('chw', 'hwc') or not (first if layout == 'chw' else last):
-            raise ValueError(f'{fn}: layout {layout!r} does not fit frames of shape {tuple(frames.shape)}')
-        chw = layout == 'chw'
-        h, w = (int(frames.shape[2]), int(frames.shape[3])) if chw else (int(frames.shape[1]), int(frames.shape[2]))
-        if int(frames.shape[0]) != V:
-            raise ValueError(f'{fn}: {int(frames.shape[0])} frames for {V} depth maps')
-        if V > 65535:
-            raise ValueError(f'{fn}: {V} views, one launch takes 65535')
-        for name, a, b in (('depth maps', H, W), ('frames', h, w)):
-            if not (1 <= a <= RD.MAX_SIDE and 1 <= b <= RD.MAX_SIDE):
-                raise ValueError(f'{fn}: {name} of {a} x {b} pixels, the kernel takes 1 .. {RD.MAX_SIDE} per side')
-        E, K = RD._matrices(fn, extrinsic, V, 'extrinsic'), RD._matrices(fn, intrinsic, V, 'intrinsic')
+        V, H, W, chw, h, w, E, K = check_views('SceneMap.add', self.device, depth, frames, extrinsic, intrinsic, layout)
         if V == 0:
             return self
         rays = torch.from_numpy(RD.camera_rays(E, K)).to(self.device)

@@ -920,6 +920,46 @@ int es_map_project(const float* boxes /*(n,9)*/, int n, const double* grid_host,
 int es_map_occupancy(unsigned char* image /*(Hm,Wm,3)*/, int Wm, int Hm, const double* grid_host, const unsigned char* occ /*(X,Y,Z)*/, int X, int Y,
                      int Z, const double* volume_host /*rmin[3], size[3]*/, const unsigned char* palette /*(C,3)*/, int C, int alpha, void* stream);
 
+/* ---- the scene in three dimensions (csrc/predict.hip) -----------------------------------------------------------
+ * The recording's depth pixels fused into one de-duplicated coloured cloud, labelled by the detections, and an occupancy volume as a
+ * mesh of exposed faces.  The exact operation order of all six kernels is written once at each kernel and restated by
+ * tests/scene_cloud_spec.py.  The cloud's state is an open-addressing table of `cap` slots (a power of two, 2 .. 2^30): tkeys int64 (-1 =
+ * empty; the caller fills it with -1 to start a cloud), tvals u64 and thits u32 (both zeroed), and counters = two u32 on the device
+ * (accepted, dropped pixels; zeroed).
+ * es_cloud_splat: depth / frames / rays as es_map_splat; grid_host = cell, z_min, z_max, max_depth (four f64 read on the HOST at the call).
+ *   A pixel with 0 < d <= max_depth, z_min <= p_z < z_max and voxel i_k = floor(p_k / cell) inside [-2^17, 2^17) on all three axes has
+ *   key = (i_x + 2^17) << 36 | (i_y + 2^17) << 18 | (i_z + 2^17) -- the coordinate key of sample 0, so es_sort_u64, es_keys_to_coords and
+ *   es_compact_mask apply to the table -- and val = (2^21 - floor(256 d)) << 24 | r << 16 | g << 8 | b.  From slot es_hash(key, cap - 1) at
+ *   most ES_CLOUD_PROBES (or cap) slots are probed linearly: the first that is empty or holds the key takes it, tvals = max(itself, val)
+ *   -- the nearest measurement wins, equal 1/256 m steps go to the larger packed colour --, thits += 1, counters[0] += 1; a pixel that
+ *   finds no slot writes nothing but counters[1] += 1.  While counters[1] stays 0 the table's CONTENT depends on no thread order and on no
+ *   order or grouping of the views (its layout may).
+ * es_cloud_mask: mask[s] = 1 iff slot s is occupied and thits[s] >= min_hits, else 0 (for es_compact_mask over the cap slots; es_sort_u64
+ *   of the selected keys then gives the cloud's row order: ascending key, x-major, then y, then z).
+ * es_cloud_points: row j with slot s = src[j]: xyz = (float)((i_k + 0.5) * cell) of sorted_keys[j], rgb = the low three bytes of tvals[s],
+ *   hits = min(thits[s], 2^31 - 1).
+ * es_cloud_label: label[i] = the smallest j whose 9-DoF box (m,9) holds point i -- |l_k| <= dims_k / 2 + grow in the box's frame, R as
+ *   es_render_project -- or -1; support[j] = the number of points labelled j (zeroed by the call, integer adds).
+ * es_occ_face_mask: occ (X,Y,Z) u8; element e = 6 * ((i*Y + j)*Z + k) + f, f = -x, +x, -y, +y, -z, +z, is 1 iff 1 <= occ[i][j][k] < C and
+ *   the neighbour across face f lies outside the volume or holds no such label, else 0 (mask: 6 X Y Z ints, for es_compact_mask).
+ * es_occ_face_quads: face row r = element src[r]: verts[4r + q] = (float)(rmin_a + (index_a + bit_a) * size_a), the four corners
+ *   counter-clockwise seen from outside (vol_host = rmin[3], size[3], read on the HOST), face_label[r] = the voxel's label.
+ * Status: -5 for a negative count; -4, nothing written and nothing launched, for cap not a power of two in 2 .. 2^30, cell <= 0, infinite
+ *   or NaN, max_depth outside (0, 4096], z_max <= z_min, a side (H, W, h, w) outside 1 .. 4096, V > 65535, min_hits < 0, grow < 0, infinite or
+ *   NaN, m > 65535, C outside 1 .. 256, a volume dimension < 1, 6 X Y Z > 2^30.  V = 0 or n = 0 is not an error and queues nothing. */
+#define ES_CLOUD_PROBES 64
+int es_cloud_splat(const float* depth /*(V,H,W)*/, int V, int H, int W, const unsigned char* frames, int chw, int h, int w,
+                   const double* rays /*(V,12)*/, const double* grid_host, int64_t* tkeys, uint64_t* tvals, unsigned int* thits, int cap,
+                   unsigned int* counters, void* stream);
+int es_cloud_mask(const int64_t* tkeys, const unsigned int* thits, int cap, int min_hits, int* mask /*(cap)*/, void* stream);
+int es_cloud_points(const int64_t* sorted_keys, const int* src, int n, const uint64_t* tvals, const unsigned int* thits, double cell,
+                    float* xyz /*(n,3)*/, unsigned char* rgb /*(n,3)*/, int* hits /*(n)*/, void* stream);
+int es_cloud_label(const float* xyz /*(n,3)*/, int n, const float* boxes /*(m,9)*/, int m, double grow, int* label /*(n)*/,
+                   int* support /*(m)*/, void* stream);
+int es_occ_face_mask(const unsigned char* occ /*(X,Y,Z)*/, int X, int Y, int Z, int C, int* mask /*(6XYZ)*/, void* stream);
+int es_occ_face_quads(const unsigned char* occ /*(X,Y,Z)*/, int X, int Y, int Z, const double* vol_host /*rmin[3], size[3]*/, const int* src,
+                      int n, float* verts /*(4n,3)*/, unsigned char* face_label /*(n)*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
